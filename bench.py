@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """Headline benchmark: eta-curvature-sweep points/s on a 4096x4096 dynamic spectrum.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 4096] [--neta 256]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 4096] [--neta 256] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints the line: the headline figure with the `config`,
+`roofline` and `gather` objects of the timed region itself.  Every other leg listed below (one-slot-group
+roofline, mixed precision, simulation screen, predicted and measured strong scaling, modeler, sspec, CPU
+baselines, the end-to-end workloads, the --shard eta bit-identity check) runs only with --full.
+--dump-outputs DIR writes what the last timed step computed (float64 .npy files; same arguments, same inputs).
 
 One *step* is one pass of the hot path over one observation per GPU: device-resident
 real dynamic spectrum [4096, 4096] -> conjugate spectrum (2-D FFT) -> for each of 256
@@ -22,9 +28,10 @@ launches them itself (same command line).  Three partitionings, none with a data
 `value` is the whole-job eta-points/s.  For N > 1 the line proves itself: `config.ranks_seen` is
 dist.get_world_size(), `config.backend` the transport, `config.per_rank_eta_per_s` the slowest / fastest
 rank's own rate, and with --shard eta `config.gathered_equals_one_gpu` says whether the gathered curve is
-bit-identical to rank 0 sweeping all curvatures alone (checked after the timed region).
+bit-identical to rank 0 sweeping all curvatures alone (checked after the timed region, with --full).
 
-Besides the contract fields the JSON line carries
+Besides the contract fields the JSON line carries (the legs timed after the headline region, modeler and
+cpu_baseline among them, with --full only)
   roofline      the dominant kernel (eigen mat-vec on the Hermitian tile-packed matrix):
                 algorithmic bytes 8 N (N+1) per matrix pass per eta -- every upper-triangle
                 element once; SURVEY.md 8d's 16 N^2 assumed the full matrix -- summed over
@@ -277,12 +284,26 @@ def parse():
     ap.add_argument("--cpu-reps", type=int, default=3, help="repetitions of the CPU sample (the median is reported)")
     ap.add_argument("--cpu-pool", type=int, default=-1,
                     help="workers of the eta-parallel oracle baseline (multiprocessing.Pool, one BLAS thread "
-                         "each: how a user parallelises the reference, dynspec.py:1715-1719); -1 = every "
+                         "each: how a user parallelises the reference, dynspec.py:1715-1719); -1 = every usable "
                          "core the host memory allows, 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline region (CPU baselines, one-slot-group roofline, mixed precision, "
+                         "simulation screen, rank shares, modeler, sspec, workloads, the multi-GPU strong leg and the --shard eta "
+                         "bit-identity check); the --*-steps, --cpu-* and --no-cpu-baseline options size them.  Without it a run "
+                         "times the headline region and nothing else")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (the curve of every observation of the step, the peak fit) to "
+                         "DIR/<name>.npy, float64, at most 64 MB in all")
     args = ap.parse_args()
-    if args.headline_only:
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.headline_only or not args.full:
         args.no_cpu_baseline, args.modeler_steps, args.mixed_steps, args.sim_steps, args.share_steps = True, 0, 0, 0, 0
         args.workload_steps = 0
+    if not args.full:
+        args.strong_steps, args.headline_only = 0, True
     return args
 
 
@@ -321,6 +342,25 @@ def make_workload(size, neta, nedge, seed, npad=0, npz=None):
     edges = np.linspace(-fd.max() / 2, fd.max() / 2, nedge)
     etas = np.geomspace(0.25, 4.0, neta) * eta_true
     return dyn, freqs, times, fd, tau, edges, etas, eta_true
+
+
+DUMP_BUDGET = 64 << 20      # bytes --dump-outputs may write in all
+
+
+def dump_outputs(path, arrays):
+    """Write each array as path/<name>.npy in float64.  Should they hold more than DUMP_BUDGET bytes together, every array is
+    cut to its share of the budget by a fixed-seed sample of its flattened elements (sorted; the same indices for the same
+    shapes), so two builds run with the same arguments still compare element for element."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    rng = np.random.default_rng(0)
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET:
+            keep = max(1, a.nbytes * DUMP_BUDGET // total // a.itemsize)
+            if keep < a.size:
+                a = a.reshape(-1)[np.sort(rng.choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def mixed_summary(run, steps, netas):
@@ -421,12 +461,29 @@ def _pool_warm(path):
     return float(_np.abs(z[::64, ::64]).sum())
 
 
+def usable_cpus():
+    """The CPUs this job may keep busy: its affinity, capped by a cgroup CPU quota and by OMP_NUM_THREADS when either is set
+    (a shared host states the job's share there; the affinity may still list every core of the machine)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        with open("/sys/fs/cgroup/cpu.max") as fh:
+            quota, period = fh.read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, -(-int(quota) // int(period))))
+    except (OSError, ValueError):
+        pass
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
+
+
 def pool_size(requested, nedge):
-    """Workers for the eta-parallel baseline: every core, capped by host memory (one oracle
+    """Workers for the eta-parallel baseline: every usable core, capped by host memory (one oracle
     gather holds about 80 M^2 bytes of temporaries) and by 64."""
     if requested >= 0:
         return requested
-    cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    cores = usable_cpus()
     avail = None
     try:
         with open("/proc/meminfo") as fh:
@@ -490,7 +547,7 @@ def simulation_screen_leg(args, size, neta, nedge, wl, main_wl, timed, ththmod):
         from scintools_amd.ththmod import fft_axis
         import torch
         t0 = time.perf_counter()
-        workers = sim_oracle.default_workers(64)
+        workers = min(sim_oracle.default_workers(64), usable_cpus())
         sim = sim_oracle.baseline_dynspec(size, 3, workers=workers)
         gen_s = time.perf_counter() - t0
         d = np.array(sim.dyn, dtype=np.float64)
@@ -970,6 +1027,14 @@ def main():
     if args.side_stream:
         torch.cuda.set_stream(torch.cuda.Stream())
     head = timed(args.objective, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the curve of every observation (all ranks' when each
+        # rank sweeps observations of its own; --shard eta gathers the one curve inside the step) and the peak fit
+        curves = head["curves"]
+        if world > 1 and not shard_eta:
+            curves = np.concatenate([g.cpu().numpy() for g in gathered])
+        dump_outputs(args.dump_outputs, {"eigenvalues" if args.objective == "eig" else "chisq": curves,
+                                         "eta_fit": np.array(head["fit"][:2], dtype=np.float64)})
 
     share_balance = None
     if shard_eta and world > 1:
@@ -998,7 +1063,7 @@ def main():
         head["info"] = dict(whole, batch=(li or {}).get("batch", 0))
 
     gathered_equal = None
-    if shard_eta and world > 1 and rank == 0:
+    if shard_eta and world > 1 and rank == 0 and args.full:
         # outside the timed region: rank 0 sweeps ALL curvatures alone; the gathered curve must be the same bits
         cs_t = ththmod.conjugate_spectrum(dyns[0], args.npad, tau, 0.0, True)
         alone = ththmod.eval_sweep(cs_t, tau, fd, etas, edges, batch=args.batch)

@@ -1,5 +1,5 @@
 """bench.py's own Python paths on the host interpreter (tests/emu/bench_probe.py), tiny sizes: the JSON contract of the
-default line incl. its mixed-precision leg, and of `--precision mixed`.  The rates are the interpreter's and mean nothing;
+--full line incl. its mixed-precision leg, of `--precision mixed`, and of the plain line with --dump-outputs.  The rates are the interpreter's and mean nothing;
 tests/test_gpu_bench_contract.py is the same contract on the GPU."""
 import json
 import os
@@ -10,17 +10,17 @@ import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROBE = os.path.join(REPO, "tests", "emu", "bench_probe.py")
-SMALL = ["--size", "128", "--neta", "6", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--modeler-steps", "0"]
+SMALL = ["--size", "128", "--neta", "6", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--modeler-steps", "0"]
 
 
-def _line(extra):
+def _line(extra, base=SMALL):
     try:
         sys.path.insert(0, os.path.join(REPO, "tests", "emu"))
         import emulated
         emulated.load()
     except (RuntimeError, OSError, subprocess.CalledProcessError) as exc:
         pytest.skip(f"host interpreter could not be built: {exc}")
-    out = subprocess.run([sys.executable, PROBE] + SMALL + extra, capture_output=True, text=True, timeout=600, cwd=REPO)
+    out = subprocess.run([sys.executable, PROBE] + base + extra, capture_output=True, text=True, timeout=600, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -75,6 +75,33 @@ def test_precision_mixed_line():
 
 
 @pytest.mark.timeout(900)
+def test_plain_line_times_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full the line is the headline region alone (no leg runs); --steps sets the timed steps (the library's launch
+    count of the timed region scales with it); --dump-outputs writes the last timed step's curve and fit in float64, the same
+    whatever the step count."""
+    import numpy as np
+    plain = ["--size", "128", "--neta", "6", "--warmup", "1"]
+    lines = []
+    for steps in (1, 3):
+        d = _line(["--steps", str(steps), "--dump-outputs", str(tmp_path / f"s{steps}")], base=plain)
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config", "roofline", "gather"):
+            assert key in d, key
+        assert d["steps"] == steps and d["value"] == pytest.approx(6 / (d["ms_per_step"] / 1e3), rel=1e-9)
+        for leg in ("mixed_precision", "simulation_screen", "modeler", "sspec", "cpu_baseline", "cpu_baseline_pool", "workloads",
+                    "strong"):
+            assert leg not in d, leg
+        assert "one_slot_group" not in d["roofline"] and "predicted_strong_scaling" not in d["config"]
+        assert list(d)[-1] == "eta_per_s" and d["eta_per_s"] == d["value"]
+        lines.append(d)
+    assert lines[1]["roofline"]["launches"] == 3 * lines[0]["roofline"]["launches"] > 0
+    for name, shape in (("eigenvalues", (1, 6)), ("eta_fit", (2,))):
+        a, b = (np.load(tmp_path / f"s{k}" / f"{name}.npy") for k in (1, 3))
+        assert a.dtype == np.float64 and a.shape == shape and np.array_equal(a, b, equal_nan=True), name
+    eigs = np.load(tmp_path / "s1" / "eigenvalues.npy")
+    assert np.all(np.isfinite(eigs)) and np.all(eigs > 0)
+
+
+@pytest.mark.timeout(900)
 def test_modeler_leg_has_its_own_roofline():
     """The `modeler` object of the line: rate, a roofline of its own whose parts add up, and the
     mixed-all leg against the float64 chi^2 curve."""
@@ -125,7 +152,7 @@ def test_two_ranks(extra):
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
-    args = ["--gpus", "2", "--size", "128", "--neta", "7", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
+    args = ["--gpus", "2", "--size", "128", "--neta", "7", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline",
             "--modeler-steps", "0"] + extra
     procs = []
     for r in range(2):

@@ -1,6 +1,6 @@
 """The driver-facing contract: bench.py prints one JSON line with the agreed fields (plus the
-roofline and cpu_baseline objects), and __graft_entry__.smoke() passes.  Small sizes: this is a
-contract check, not a measurement."""
+roofline object; with --full also cpu_baseline and the other legs), and __graft_entry__.smoke()
+passes.  Small sizes: this is a contract check, not a measurement."""
 import json
 import os
 import subprocess
@@ -14,7 +14,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_json_contract():
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--size", "512", "--neta", "16",
-                          "--steps", "2", "--warmup", "1", "--cpu-sample", "2", "--cpu-reps", "2", "--cpu-pool", "0"],
+                          "--steps", "2", "--warmup", "1", "--full", "--cpu-sample", "2", "--cpu-reps", "2", "--cpu-pool", "0"],
                          capture_output=True, text=True, timeout=600, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -55,11 +55,41 @@ def test_bench_json_contract():
     assert d["gather_frac_alone"] == d["gather"]["one_slot_group"]["frac"] and d["sspec_ms"] == d["sspec"]["512x512"]["ms"]
 
 
+def test_bench_plain_line_and_its_dumped_outputs(tmp_path):
+    """The plain command (no --full) times the headline region alone and --dump-outputs writes the last timed step's curve:
+    the same bits for any step count, and the oracle's Eval_calc values on a sample."""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    from oracle import thth_oracle
+    lines = []
+    for steps in (1, 3):
+        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--size", "512", "--neta", "16",
+                              "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(tmp_path / f"s{steps}")],
+                             capture_output=True, text=True, timeout=600, cwd=REPO)
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d, key
+        assert d["steps"] == steps and d["value"] == pytest.approx(16 / (d["ms_per_step"] / 1e3), rel=1e-9)
+        for leg in ("mixed_precision", "simulation_screen", "modeler", "sspec", "cpu_baseline", "workloads"):
+            assert leg not in d, leg
+        lines.append(d)
+    eigs = np.load(tmp_path / "s1" / "eigenvalues.npy")
+    assert eigs.dtype == np.float64 and eigs.shape == (1, 16)
+    assert np.array_equal(eigs, np.load(tmp_path / "s3" / "eigenvalues.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "eta_fit.npy"), np.load(tmp_path / "s3" / "eta_fit.npy"), equal_nan=True)
+    dyn, freqs, times, fd, tau, edges, etas, eta_true = bench.make_workload(512, 16, 512, seed=3)
+    CS = thth_oracle.conjugate_spectrum(dyn, 0)
+    for i in (0, 7, 15):
+        assert eigs[0, i] == pytest.approx(thth_oracle.Eval_calc(CS, tau, fd, etas[i], edges), rel=1e-9), i
+
+
 def test_bench_default_line_times_the_workloads():
-    """At a size with 4 x 4 chunks the default line also carries `workloads`: Dynspec.fit_thetatheta, calc_wavefield, the tutorial
+    """At a size with 4 x 4 chunks the --full line also carries `workloads`: Dynspec.fit_thetatheta, calc_wavefield, the tutorial
     recipe and fit_arc timed on the GPU alone (their CPU samples stay behind --workload X)."""
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--size", "1024", "--neta", "16", "--steps", "1", "--warmup", "1",
-                          "--no-cpu-baseline", "--modeler-steps", "0", "--mixed-steps", "0", "--sim-steps", "0", "--share-steps", "0",
+                          "--full", "--no-cpu-baseline", "--modeler-steps", "0", "--mixed-steps", "0", "--sim-steps", "0", "--share-steps", "0",
                           "--workload-steps", "1"], capture_output=True, text=True, timeout=900, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])

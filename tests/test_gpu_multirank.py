@@ -155,7 +155,7 @@ def test_bench_shard_eta_gathers_the_one_gpu_curve():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--shard", "eta", "--size", "512",
-                          "--neta", "17", "--steps", "2", "--warmup", "1", "--modeler-steps", "0"],
+                          "--neta", "17", "--steps", "2", "--warmup", "1", "--full", "--modeler-steps", "0"],
                          capture_output=True, text=True, timeout=800, cwd=REPO, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

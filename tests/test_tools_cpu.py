@@ -36,6 +36,15 @@ def test_bench_pool_size_is_bounded_by_memory_and_cores():
     assert bench.pool_size(-1, 16384) <= bench.pool_size(-1, 1024)
 
 
+def test_bench_pools_keep_to_the_jobs_share_of_the_host(monkeypatch):
+    """The --full legs' process pools are sized by the CPUs the job may use: OMP_NUM_THREADS caps the affinity."""
+    import bench
+    monkeypatch.delenv("OMP_NUM_THREADS", raising=False)
+    assert 1 <= bench.usable_cpus() <= len(os.sched_getaffinity(0))
+    monkeypatch.setenv("OMP_NUM_THREADS", "1")
+    assert bench.usable_cpus() == 1 and bench.pool_size(-1, 1024) == 1
+
+
 def test_bench_workload_is_the_baseline_config():
     import bench
     dyn, freqs, times, fd, tau, edges, etas, eta_true = bench.make_workload(256, 32, 256, seed=3)

@@ -4,7 +4,7 @@
 #   gpurun --timeout 900 -- 'bash tools/gpu_run.sh <sub-command> [tag] [extra bench.py arguments]'
 # Output goes to gpurun_out/<tag>_*; summaries worth keeping are copied into profiles/ by hand.
 #   suite    [tag]          pytest -m gpu (whole suite, durations)
-#   bench    [tag] [args]   the driver's bench command (--gpus 1 --steps 20 --warmup 5) + extra args
+#   bench    [tag] [args]   the driver's bench command (--gpus 1 --steps 20 --warmup 5) with --full (every leg) + extra args
 #   quick    [tag] [args]   bench.py --steps 5 --warmup 2 --headline-only (no CPU baseline, no modeler / mixed / one-slot-group legs) + extra args
 #   configs  [tag]          BASELINE configs 4 / 5, npad = 3 and the 4096^2 reference-Simulation screen
 #   trace    [tag] [args]   rocprofv3 --kernel-trace --stats of a 3-step bench -> per-kernel stats + interval unions
@@ -16,7 +16,7 @@
 #   fft      [tag]          kernel trace + PMC passes of tools/time_fft.py (calc_sspec and CS, 2048^2 .. 8192^2)
 #   sspecroof [tag]         FETCH / WRITE / instruction-count passes of calc_sspec alone at 4096^2 and 8192^2 -> <tag>_sspec_roofline_<size>.json (bench.py: sspec.roofline)
 #   probes   [tag]          tools/probes/*.hip (stream ceiling, the round-2 and round-3 mat-vec loops with their parts switchable, f64 MFMA layout)
-#   mixed    [tag] [args]   the mixed-precision sweep: a 3-step bench with its --mixed-steps leg (rate, bytes by operand, curve against
+#   mixed    [tag] [args]   the mixed-precision sweep: a 3-step --full bench with its --mixed-steps leg (rate, bytes by operand, curve against
 #                           the float64 one), then tests/test_gpu_zz_mixed.py
 #   workloads [tag]         bench.py --workload fit_thetatheta | wavefield | tutorial_fit | fit_arc (the (f) rows end to end, CPU port beside them)
 #   all      [tag]          suite, bench, configs, trace, modeler, pmc, pmc_modeler, counters, fft, sspecroof, workloads, mixed  (the closing call of a round)
@@ -32,7 +32,7 @@ suite() {
   grep -E "passed|failed|^FAILED|^ERROR|rc=" $O/${TAG}_pytest.log | tail -8
 }
 bench() {
-  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 $EXTRA > $O/${TAG}_bench_n1.json 2> $O/${TAG}_bench.err; echo "bench rc=$?"
+  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full $EXTRA > $O/${TAG}_bench_n1.json 2> $O/${TAG}_bench.err; echo "bench rc=$?"
   head -c 400 $O/${TAG}_bench_n1.json; echo; tail -2 $O/${TAG}_bench.err
 }
 quick() {
@@ -43,8 +43,8 @@ configs() {
   timeout 300 python bench.py --size 2048 --obs-total 64 --steps 2 --warmup 1 $QUICK > $O/${TAG}_bench_cfg4_64obs.json 2>> $O/${TAG}_bench.err
   timeout 300 python bench.py --size 8192 --neta 64 --steps 2 --warmup 1 $QUICK > $O/${TAG}_bench_cfg5_8192.json 2>> $O/${TAG}_bench.err
   timeout 300 python bench.py --npad 3 --steps 2 --warmup 1 $QUICK > $O/${TAG}_bench_npad3.json 2>> $O/${TAG}_bench.err
-  timeout 600 python tests/tools/make_sim_input.py 4096 3 /tmp/sim4096.npz > $O/${TAG}_sim_input.txt 2>&1
-  timeout 300 python bench.py --dyn-npz /tmp/sim4096.npz --steps 3 --warmup 1 --cpu-pool 0 --cpu-sample 2 --modeler-steps 0 > $O/${TAG}_bench_sim4096.json 2>> $O/${TAG}_bench.err
+  timeout 600 python tests/tools/make_sim_input.py 4096 3 $TMPDIR/sim4096.npz > $O/${TAG}_sim_input.txt 2>&1
+  timeout 300 python bench.py --dyn-npz $TMPDIR/sim4096.npz --steps 3 --warmup 1 --full --cpu-pool 0 --cpu-sample 2 --modeler-steps 0 > $O/${TAG}_bench_sim4096.json 2>> $O/${TAG}_bench.err
   for f in cfg4_64obs cfg5_8192 npad3 sim4096; do python tools/bench_line.py $O/${TAG}_bench_$f.json; done
 }
 trace_of() {  # name, bench arguments
@@ -120,7 +120,7 @@ print('  ', round(d['value'],4), 's; cpu port', round(d['cpu_baseline']['value']
   done
 }
 mixed() {
-  timeout 200 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --modeler-steps 0 --mixed-steps 3 $EXTRA > $O/${TAG}_mixed.json 2> $O/${TAG}_mixed.err; echo "bench rc=$?"
+  timeout 200 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --modeler-steps 0 --mixed-steps 3 $EXTRA > $O/${TAG}_mixed.json 2> $O/${TAG}_mixed.err; echo "bench rc=$?"
   python tools/bench_line.py $O/${TAG}_mixed.json; python -c "
 import json,sys
 d=json.loads([l for l in open('$O/${TAG}_mixed.json') if l.startswith('{')][-1]); m=d.get('mixed_precision',{})
