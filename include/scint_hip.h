@@ -64,6 +64,15 @@ typedef struct {
     double fd1_step;       /* fd[1]-fd[0]     (rev_map bin edges, :211-213)     */
 } scint_cs_geom;
 
+/* Geometry of a conjugate spectrum for the thin-screen map two_curve_map (ththmod.py:1557-1636), which indexes from the
+ * SECOND sample of each axis: tau_inv = ((eta1 th1^2 - eta2 th2^2) - tau[1] + dtau/2) // dtau and
+ * fd_inv = ((th1 - th2) - fd[1] + dfd/2) // dfd.  Host-computed with the reference's NumPy expressions. */
+typedef struct {
+    int64_t ntau, nfd;     /* CS shape: tau is the slow axis                    */
+    double tau1, dtau;     /* tau[1], np.diff(tau).mean()            [us]       */
+    double fd1, dfd;       /* fd[1],  np.diff(fd).mean()             [mHz]      */
+} scint_thin_geom;
+
 /* ---- diagnostics -------------------------------------------------------- */
 int32_t scint_version(void);
 /* HOST buffer; copies the calling thread's last error text. */
@@ -480,6 +489,47 @@ int32_t scint_block_std(const double* a, int64_t ld, int64_t nc, int64_t r0, int
 int32_t scint_fft2_workspace_bytes(int64_t rows, int64_t cols, size_t* bytes /*HOST*/);
 int32_t scint_fft2(const scint_c128* in, scint_c128* out, int64_t rows, int64_t cols,
                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- thin-screen curvature search: two_curve_map + singularvalue_calc (ththmod.py:496-513, 1557-1636) ----------------
+ * The 'thin' fitting procedure of Dynspec.prep_thetatheta (dynspec.py:1480-1516) models only the region near the arclet apexes:
+ * a RECTANGULAR theta-theta map thth[theta2, theta1] (rows: the arclet centres th2[M2], columns: the main-arc centres th1[M1],
+ * both (edges[1:] + edges[:-1]) / 2 with no re-centring), cropped to |centre| < sqrt(tau.max() / eta) on each axis, with the
+ * reduced columns |centre| < centerCut set to zero, and its largest singular value in place of np.linalg.svd(thth_red)[1][0].
+ * ranges (HOST, 6 int32 per map): r0, n2 = the kept theta2 centres [r0, r0 + n2); c0, n1 = the kept theta1 centres
+ * [c0, c0 + n1); cut0, cut1 = the reduced columns [cut0, cut1) that are zeroed.  The host computes them with the reference's
+ * own masks (each must be one run of centres: edges from np.linspace).  check != 0: the grid may reach fd_inv < -nfd, where
+ * NumPy's fancy index raises IndexError (the wrap of -nfd <= fd_inv < 0 is reproduced); the whole M2 x M1 grid is then tested.
+ *
+ * scint_two_curve_map: thth_out[n2][n1] (every element written); *raise_out (device int32) = 1 if NumPy would raise.
+ *   Synchronous.  Workspace: scint_two_curve_map_workspace_bytes() (the job table).
+ * scint_sv_sweep_multi: sigma_1 of every map of a fit_thetatheta -- the per-chunk loops of single_search_thin (ththmod.py:
+ *   588-643) over every (chunk, eta) pair in one call, as scint_eval_sweep_multi does for 'standard'.  Map e is built from
+ *   cs_stack + cs_index[e] * cs_stride with geoms[cs_index[e]], th1_stack[cs_index[e]][M1], th2_stack[cs_index[e]][M2], the
+ *   curvatures etas1[e] (main arc) and etas2[e] (arclets), ranges[e][6] and check[e].  sigma_1 = sqrt(lambda_max(A^H A)) by
+ *   float64 Lanczos with the Ritz-residual rule of the eigenvalue sweeps (residual <= tol lambda, on A^H A), from the conjugated
+ *   middle row (the constant vector if that row is zero); a map whose Krylov space is complete first is exact (a single column:
+ *   its 2-norm; the all-zero map: 0).  A is read from HBM once per Lanczos step (eigen.hip, sv_matvec_kernel).  The maps are
+ *   built and resident `batch` at a time (each slab holds an M2 x M1 map).  Results are bit-reproducible and do not depend on
+ *   `batch` or on which maps share a call.  Mixed precision (scint_sweep_precision) does not apply: always float64.
+ *   Outputs (device): sv_out[neta] (NaN unless status 0), status_out[neta]: 0, SCINT_E_NOCONV, SCINT_E_EMPTY (no kept row or
+ *   column), SCINT_E_NONFINITE, or SCINT_E_ARG = NumPy would raise IndexError in two_curve_map; iters_out[neta] Lanczos steps.
+ *   At most 16384 theta1 centres.  Synchronous.  Workspace: scint_sv_sweep_multi_workspace_bytes(). */
+int32_t scint_two_curve_map_workspace_bytes(size_t* bytes /*HOST*/);
+int32_t scint_two_curve_map(const scint_c128* cs, const scint_thin_geom* geom /*HOST*/,
+                            const double* th1, int64_t M1, const double* th2, int64_t M2,
+                            double eta1, double eta2, const int32_t* ranges /*HOST[6]*/, int32_t check,
+                            scint_c128* thth_out, int32_t* raise_out, void* workspace, size_t workspace_bytes,
+                            void* stream);
+int32_t scint_sv_sweep_multi_workspace_bytes(int64_t M1, int64_t M2, int64_t neta, int64_t batch, int32_t max_iter,
+                                             int64_t ncs, size_t* bytes /*HOST*/);
+int32_t scint_sv_sweep_multi(const scint_c128* cs_stack, int64_t ncs, int64_t cs_stride,
+                             const int32_t* cs_index /*HOST*/, const scint_thin_geom* geoms /*HOST*/,
+                             const double* th1_stack, int64_t M1, const double* th2_stack, int64_t M2,
+                             const int32_t* ranges /*HOST[neta][6]*/, const int32_t* check /*HOST*/,
+                             const double* etas1 /*HOST*/, const double* etas2 /*HOST*/, int64_t neta,
+                             double tol, int32_t max_iter, int64_t batch,
+                             double* sv_out, int32_t* status_out, int32_t* iters_out,
+                             void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

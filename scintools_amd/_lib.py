@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(HERE, "libscint_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "scint_hip.h")
 
 SCINT_OK = 0
+SCINT_E_ARG = 1
 SCINT_E_NOCONV = 4
 SCINT_E_EMPTY = 5
 SCINT_E_NONFINITE = 6
@@ -31,6 +32,13 @@ class CsGeom(ctypes.Structure):
                 ("fd0", c_double), ("dfd", c_double),
                 ("tau_max", c_double), ("fd_max", c_double),
                 ("tau1_step", c_double), ("fd1_step", c_double)]
+
+
+class ThinGeom(ctypes.Structure):
+    """Mirror of scint_thin_geom."""
+    _fields_ = [("ntau", c_int64), ("nfd", c_int64),
+                ("tau1", c_double), ("dtau", c_double),
+                ("fd1", c_double), ("dfd", c_double)]
 
 
 _P = c_void_p  # device pointers travel as integers
@@ -103,11 +111,18 @@ _SIGNATURES = {
     "scint_row_nanmean": ([_P, c_int64, c_int64, c_int64, c_int64, _P, c_int64, c_int64, _P, _P], c_int32),
     "scint_block_std": ([_P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, _P, _P, c_size_t, _P], c_int32),
     "scint_fft2_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
+    "scint_two_curve_map_workspace_bytes": ([POINTER(c_size_t)], c_int32),
+    "scint_two_curve_map": ([_P, POINTER(ThinGeom), _P, c_int64, _P, c_int64, c_double, c_double, POINTER(c_int32), c_int32,
+                             _P, _P, _P, c_size_t, _P], c_int32),
+    "scint_sv_sweep_multi_workspace_bytes": ([c_int64, c_int64, c_int64, c_int64, c_int32, c_int64, POINTER(c_size_t)], c_int32),
+    "scint_sv_sweep_multi": ([_P, c_int64, c_int64, POINTER(c_int32), POINTER(ThinGeom), _P, c_int64, _P, c_int64,
+                              POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double), c_int64,
+                              c_double, c_int32, c_int64, _P, _P, _P, _P, c_size_t, _P], c_int32),
     "scint_fft2": ([_P, _P, c_int64, c_int64, _P, c_size_t, _P], c_int32),
 }
 
 _lib = None
-ABI_VERSION = 107          # scint_version() of the library these signatures describe (csrc/capi.hip)
+ABI_VERSION = 108          # scint_version() of the library these signatures describe (csrc/capi.hip)
 
 
 def header_symbols():

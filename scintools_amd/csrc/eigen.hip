@@ -463,3 +463,443 @@ extern "C" int32_t scint_eigh_top(const scint_c128* a, int64_t n, const scint_c1
     return SCINT_OK;
 }
 
+
+// ==============================================================================
+// Largest singular value of rectangular theta-theta maps: the thin-screen search
+// (singularvalue_calc, ththmod.py:496-513, swept by single_search_thin, :516-712)
+// ==============================================================================
+// The reference takes S[0] of a dense np.linalg.svd of every map.  Here: Lanczos on the Hermitian
+// B = A^H A (n1 x n1, A = the n2 x n1 map), sigma_1 = sqrt(lambda_max(B)), with the same tridiagonal
+// machinery (lanczos_check_kernel: Sturm-count multisection of T_k, Ritz residual beta_k |s_k| <= tol theta).
+// Float64 only: the mixed-precision mode of the eigenvalue sweeps (scint_sweep_precision) does not apply.
+//
+// Per Lanczos step j (batched over the resident maps in blockIdx.y):
+//   sv_matvec_kernel   a workgroup owns a strip of R rows: for each row (two at a time when the row is
+//                      short) it loads the row into registers, forms y_r = A_r q_j (fixed-tree block
+//                      reduction) and adds conj(A_r) y_r to its partial of z = A^H A q_j while the row is
+//                      still in registers -- A is read from HBM once per step (16 n1 n2 bytes).  The
+//                      partials [G][n1] are summed in block order by
+//   sv_reduce_kernel   z = sum_b partial_b; u = z - beta_j q_{j-1}; partial q_j^H u
+//   sv_update_kernel   alpha_j; w = u - alpha_j q_j; partial |w|^2
+// and every 8 steps lanczos_check_kernel.  R and G depend on n2 only and every sum has a fixed order,
+// so a map's result does not depend on which maps share its launches.
+namespace scint {
+
+constexpr int kSvMinRows = 4;
+
+struct SvJob {
+    const cplx* A;            // [n2][n1]
+    int32_t n1, n2, max_steps, R, G, cls;
+    cplx* W[2];               // ping-pong work vectors [n1]
+    cplx* Q;                  // [2][n1] ring of q vectors
+    cplx* zpart;              // [G][n1]
+    double* alpha;            // [max_steps + 1]
+    double* beta;             // [max_steps + 2]
+    double* apart;            // [ceil(n1 / 256)]
+    double* npart;            // [ceil(n1 / 256)]
+    int32_t* state;           // [4] (shared with the check kernel's LanczosJob)
+    double* lam;              // lambda_max(B) from the check kernel
+    int32_t* status;          // from the check kernel
+    int32_t* iters;
+    const int32_t* raise;     // the gather's "NumPy would raise" word
+};
+
+__host__ __device__ inline int sv_rows_per_group(int n2) {
+    const int r = (n2 + 255) / 256;
+    return r > kSvMinRows ? r : kSvMinRows;
+}
+
+__device__ inline double sv_beta(const SvJob& jb) {
+    return sqrt(sum_partials(jb.npart, (jb.n1 + kVecBlock - 1) / kVecBlock));
+}
+
+// q_j = w_j / beta_j; at j = 0 with a zero start vector the defined fallback is the constant unit vector
+__device__ inline cplx sv_q(const SvJob& jb, const cplx* w, int c, int step, double beta) {
+    if (step == 0 && beta == 0.0) return mk(1.0 / sqrt((double)jb.n1), 0.0);
+    const double inv = beta > 0.0 ? 1.0 / beta : 0.0;
+    const cplx v = w[c];
+    return mk(v.x * inv, v.y * inv);
+}
+
+// w_0 = conj(row n2/2 of A) (the middle row, as Eval_calc starts from, ththmod.py:398); partial |w_0|^2.
+// Maps the gather flagged, maps with an empty side and single-column maps take no Lanczos steps.
+__global__ void __launch_bounds__(kVecBlock) sv_init_kernel(const SvJob* jobs) {
+    __shared__ double red[kVecBlock / 64];
+    const SvJob jb = jobs[blockIdx.y];
+    const int n1 = jb.n1;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const bool skip = *jb.raise != 0 || n1 < 2 || jb.n2 < 1;
+        jb.state[0] = skip ? 1 : 0;
+        jb.state[1] = 0;
+    }
+    if (n1 < 2 || jb.n2 < 1 || (int)blockIdx.x * kVecBlock >= n1) return;
+    const int c = blockIdx.x * kVecBlock + threadIdx.x;
+    double p = 0.0;
+    if (c < n1) {
+        const cplx v = conj(jb.A[(int64_t)(jb.n2 / 2) * n1 + c]);
+        jb.W[0][c] = v;
+        p = norm2(v);
+    }
+    p = block_sum(p, red);
+    if (threadIdx.x == 0) jb.npart[blockIdx.x] = p;
+}
+
+template <int NT, int K, int ROWS>
+__global__ void __launch_bounds__(NT) sv_matvec_kernel(const SvJob* jobs, int step, int cls) {
+    constexpr int NW = NT / 64;
+    __shared__ cplx red[2][NW][ROWS];
+    const SvJob jb = jobs[blockIdx.y];
+    if (jb.cls != cls || (int)blockIdx.x >= jb.G || step >= jb.max_steps || jb.state[0]) return;
+    const int n1 = jb.n1, n2 = jb.n2;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const cplx* __restrict__ win = (step & 1) ? jb.W[1] : jb.W[0];
+    const double beta = sv_beta(jb);
+    cplx q[K], z[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int c = threadIdx.x + NT * k;
+        q[k] = c < n1 ? sv_q(jb, win, c, step, beta) : mk(0.0, 0.0);
+        z[k] = mk(0.0, 0.0);
+    }
+    const int r_begin = blockIdx.x * jb.R;
+    const int r_end = min(r_begin + jb.R, n2);
+    int par = 0;
+    for (int r0 = r_begin; r0 < r_end; r0 += ROWS) {
+        cplx a[ROWS][K];
+#pragma unroll
+        for (int rr = 0; rr < ROWS; ++rr) {
+            const int row = r0 + rr;
+            const cplx* __restrict__ rowp = jb.A + (int64_t)(row < r_end ? row : r0) * n1;
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const int c = threadIdx.x + NT * k;
+                a[rr][k] = (row < r_end && c < n1) ? gload_nt(rowp + c) : mk(0.0, 0.0);
+            }
+        }
+        cplx s[ROWS];
+#pragma unroll
+        for (int rr = 0; rr < ROWS; ++rr) {
+            s[rr] = mk(0.0, 0.0);
+#pragma unroll
+            for (int k = 0; k < K; ++k) s[rr] = s[rr] + a[rr][k] * q[k];
+            s[rr] = wave_sum(s[rr]);
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int rr = 0; rr < ROWS; ++rr) red[par][wave][rr] = s[rr];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int rr = 0; rr < ROWS; ++rr) {
+            cplx y = red[par][0][rr];
+            for (int w = 1; w < NW; ++w) y = y + red[par][w][rr];
+#pragma unroll
+            for (int k = 0; k < K; ++k) z[k] = z[k] + conj(a[rr][k]) * y;
+        }
+        par ^= 1;
+    }
+    cplx* __restrict__ zp = jb.zpart + (int64_t)blockIdx.x * n1;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int c = threadIdx.x + NT * k;
+        if (c < n1) zp[c] = z[k];
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) jb.beta[step] = beta;
+}
+
+__global__ void __launch_bounds__(kVecBlock) sv_reduce_kernel(const SvJob* jobs, int step) {
+    __shared__ double red[kVecBlock / 64];
+    const SvJob jb = jobs[blockIdx.y];
+    const int n1 = jb.n1;
+    if (blockIdx.x * kVecBlock >= n1 || step >= jb.max_steps || jb.state[0]) return;
+    const cplx* __restrict__ win = (step & 1) ? jb.W[1] : jb.W[0];
+    cplx* __restrict__ wout = (step & 1) ? jb.W[0] : jb.W[1];
+    const double beta = sv_beta(jb);
+    const int c = blockIdx.x * kVecBlock + threadIdx.x;
+    double p = 0.0;
+    if (c < n1) {
+        cplx z = jb.zpart[c];
+        for (int b = 1; b < jb.G; ++b) z = z + jb.zpart[(int64_t)b * n1 + c];
+        const cplx q = sv_q(jb, win, c, step, beta);
+        cplx u = z;
+        if (step > 0) {
+            const cplx qp = jb.Q[(int64_t)((step + 1) & 1) * n1 + c];
+            u = mk(u.x - beta * qp.x, u.y - beta * qp.y);
+        }
+        jb.Q[(int64_t)(step & 1) * n1 + c] = q;
+        wout[c] = u;
+        p = q.x * u.x + q.y * u.y;      // Re(conj(q) u)
+    }
+    p = block_sum(p, red);
+    if (threadIdx.x == 0) jb.apart[blockIdx.x] = p;
+}
+
+__global__ void __launch_bounds__(kVecBlock) sv_update_kernel(const SvJob* jobs, int step) {
+    __shared__ double red[kVecBlock / 64];
+    const SvJob jb = jobs[blockIdx.y];
+    const int n1 = jb.n1;
+    if (blockIdx.x * kVecBlock >= n1 || step >= jb.max_steps || jb.state[0]) return;
+    const int nvb = (n1 + kVecBlock - 1) / kVecBlock;
+    const double alpha = sum_partials(jb.apart, nvb);
+    cplx* __restrict__ w = (step & 1) ? jb.W[0] : jb.W[1];
+    const cplx* __restrict__ q = jb.Q + (int64_t)(step & 1) * n1;
+    const int c = blockIdx.x * kVecBlock + threadIdx.x;
+    double p = 0.0;
+    if (c < n1) {
+        const cplx u = w[c], qv = q[c];
+        const cplx v = mk(u.x - alpha * qv.x, u.y - alpha * qv.y);
+        w[c] = v;
+        p = norm2(v);
+    }
+    p = block_sum(p, red);
+    if (threadIdx.x == 0) {
+        jb.npart[blockIdx.x] = p;
+        if (blockIdx.x == 0) jb.alpha[step] = alpha;
+    }
+}
+
+// sigma_1 and the status of every map of the batch.  A breakdown right after the first step (B q_0 = alpha_0 q_0 exactly,
+// the all-zero map among them) is exact: lambda = alpha_0.  A single column needs no iteration: sigma = its 2-norm (rows in order).
+__global__ void __launch_bounds__(64) sv_finish_kernel(const SvJob* jobs, int njobs, double* sv_out, int32_t* status_out,
+                                                       int32_t* iters_out) {
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    if (j >= njobs) return;
+    const SvJob jb = jobs[j];
+    double sv;
+    int32_t st, it;
+    if (*jb.raise) { sv = nan(""); st = SCINT_E_ARG; it = 0; }
+    else if (jb.n1 < 1 || jb.n2 < 1) { sv = nan(""); st = SCINT_E_EMPTY; it = 0; }
+    else if (jb.n1 == 1) {
+        double s = 0.0;
+        for (int r = 0; r < jb.n2; ++r) s += norm2(jb.A[r]);
+        sv = sqrt(s);
+        st = isfinite(sv) ? SCINT_OK : SCINT_E_NONFINITE;
+        it = 0;
+    } else {
+        st = *jb.status;
+        it = *jb.iters;
+        double lam = *jb.lam;
+        if (st == SCINT_OK && it >= 1 && jb.beta[1] == 0.0 && isfinite(jb.alpha[0])) lam = jb.alpha[0];
+        sv = st == SCINT_OK ? sqrt(fabs(lam)) : nan("");
+    }
+    sv_out[j] = sv;
+    status_out[j] = st;
+    iters_out[j] = it;
+}
+
+template <int NT, int K>
+static void launch_sv_matvec(const SvJob* jobs_dev, dim3 grid, int step, int cls, hipStream_t stream) {
+    constexpr int ROWS = K <= 8 ? 2 : 1;
+    hipLaunchKernelGGL((sv_matvec_kernel<NT, K, ROWS>), grid, dim3(NT), 0, stream, jobs_dev, step, cls);
+}
+
+// class of a map by its row length: 256 threads x K columns each (K = 1, 2, 4, 8, 16), then 512 x 16 and 1024 x 16
+// (a thread keeps K elements of the row, of q and of its z partial in registers: K = 16 is the most that fits)
+static int sv_class(int n1) {
+    if (n1 <= 256) return 0;
+    if (n1 <= 512) return 1;
+    if (n1 <= 1024) return 2;
+    if (n1 <= 2048) return 3;
+    if (n1 <= 4096) return 4;
+    if (n1 <= 8192) return 5;
+    return 6;
+}
+constexpr int kSvClasses = 7;
+constexpr int64_t kSvMaxCols = 16384;
+
+static void launch_sv_class(const SvJob* jobs_dev, int cls, unsigned gmax, unsigned nj, int step, hipStream_t stream) {
+    const dim3 grid(gmax, nj);
+    switch (cls) {
+        case 0: launch_sv_matvec<256, 1>(jobs_dev, grid, step, cls, stream); break;
+        case 1: launch_sv_matvec<256, 2>(jobs_dev, grid, step, cls, stream); break;
+        case 2: launch_sv_matvec<256, 4>(jobs_dev, grid, step, cls, stream); break;
+        case 3: launch_sv_matvec<256, 8>(jobs_dev, grid, step, cls, stream); break;
+        case 4: launch_sv_matvec<256, 16>(jobs_dev, grid, step, cls, stream); break;
+        case 5: launch_sv_matvec<512, 16>(jobs_dev, grid, step, cls, stream); break;
+        default: launch_sv_matvec<1024, 16>(jobs_dev, grid, step, cls, stream); break;
+    }
+}
+
+struct SvSlab {      // byte offsets inside one resident map's slab
+    size_t A, W0, W1, Q, zpart, alpha, beta, apart, npart, result, lam, status, iters, total;
+};
+static SvSlab sv_slab(int64_t n1max, int64_t n2max, int max_steps) {
+    SvSlab L;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { off = align_up(off, 256); size_t o = off; off += bytes; return o; };
+    const int64_t gmax = ceil_div(std::max<int64_t>(n2max, 1), sv_rows_per_group((int)std::max<int64_t>(n2max, 1)));
+    L.A = take(sizeof(cplx) * (size_t)n1max * (size_t)n2max);
+    L.W0 = take(sizeof(cplx) * n1max);
+    L.W1 = take(sizeof(cplx) * n1max);
+    L.Q = take(sizeof(cplx) * 2 * n1max);
+    L.zpart = take(sizeof(cplx) * (size_t)gmax * n1max);
+    L.alpha = take(sizeof(double) * (max_steps + 2));
+    L.beta = take(sizeof(double) * (max_steps + 2));
+    L.apart = take(sizeof(double) * ceil_div(n1max, kVecBlock));
+    L.npart = take(sizeof(double) * ceil_div(n1max, kVecBlock));
+    L.result = take(sizeof(double) * 4);
+    L.lam = take(sizeof(double) * 2);
+    L.status = take(sizeof(int32_t) * 2);
+    L.iters = take(sizeof(int32_t) * 2);
+    L.total = align_up(off, 256);
+    return L;
+}
+// per batch: the slabs, the two job tables, the geometry table and the raise words
+static size_t sv_batch_bytes(int64_t n1max, int64_t n2max, int max_steps, int64_t batch, int64_t ncs) {
+    const SvSlab L = sv_slab(n1max, n2max, max_steps);
+    return L.total * (size_t)batch + align_up(sizeof(SvJob) * batch, 256) + align_up(sizeof(LanczosJob) * batch, 256) +
+           align_up(sizeof(ThinJob) * batch, 256) + align_up(sizeof(ThinGeomDev) * ncs, 256) +
+           align_up(sizeof(int32_t) * batch, 256) + align_up(sizeof(int32_t) * 4 * batch, 256) + 4096;
+}
+
+}  // namespace scint
+
+extern "C" int32_t scint_sv_sweep_multi_workspace_bytes(int64_t M1, int64_t M2, int64_t neta, int64_t batch,
+                                                        int32_t max_iter, int64_t ncs, size_t* bytes) {
+    SCINT_REQUIRE(bytes && M1 >= 1 && M2 >= 1 && neta >= 1 && batch >= 1 && max_iter >= 1 && ncs >= 1,
+                  "sv_sweep_multi_workspace_bytes: bad arguments");
+    SCINT_REQUIRE(M1 <= kSvMaxCols, "sv_sweep_multi_workspace_bytes: more than 16384 theta1 centres");
+    const int steps = (int)std::min<int64_t>(max_iter, M1);
+    *bytes = sv_batch_bytes(M1, M2, steps, std::min(batch, neta), ncs);
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_sv_sweep_multi(const scint_c128* cs_stack, int64_t ncs, int64_t cs_stride,
+                                        const int32_t* cs_index, const scint_thin_geom* geoms,
+                                        const double* th1_stack, int64_t M1, const double* th2_stack, int64_t M2,
+                                        const int32_t* ranges, const int32_t* check, const double* etas1,
+                                        const double* etas2, int64_t neta, double tol, int32_t max_iter, int64_t batch,
+                                        double* sv_out, int32_t* status_out, int32_t* iters_out, void* workspace,
+                                        size_t workspace_bytes, void* stream_) {
+    SCINT_REQUIRE(cs_stack && cs_index && geoms && th1_stack && th2_stack && ranges && check && etas1 && etas2 && sv_out &&
+                  status_out && iters_out && workspace, "sv_sweep_multi: null pointer");
+    SCINT_REQUIRE(ncs >= 1 && neta >= 1 && batch >= 1 && max_iter >= 1 && tol > 0, "sv_sweep_multi: bad arguments");
+    SCINT_REQUIRE(M1 >= 1 && M2 >= 1 && M1 <= kSvMaxCols && M2 < (1 << 30), "sv_sweep_multi: bad grid sizes");
+    for (int64_t c = 0; c < ncs; ++c)
+        SCINT_REQUIRE(geoms[c].ntau >= 2 && geoms[c].nfd >= 2 && geoms[c].dtau > 0 && geoms[c].dfd > 0 &&
+                      geoms[c].ntau * geoms[c].nfd <= cs_stride, "sv_sweep_multi: bad geometry");
+    int64_t n1max = 1, n2max = 1;
+    for (int64_t e = 0; e < neta; ++e) {
+        const int32_t* r = ranges + 6 * e;
+        SCINT_REQUIRE(cs_index[e] >= 0 && cs_index[e] < ncs, "sv_sweep_multi: cs_index out of range");
+        SCINT_REQUIRE(r[0] >= 0 && r[1] >= 0 && r[0] + (int64_t)r[1] <= M2 && r[2] >= 0 && r[3] >= 0 &&
+                      r[2] + (int64_t)r[3] <= M1 && r[4] >= 0 && r[4] <= r[5] && r[5] <= r[3],
+                      "sv_sweep_multi: crop or cut outside the grids");
+        n2max = std::max<int64_t>(n2max, r[1]);
+        n1max = std::max<int64_t>(n1max, r[3]);
+    }
+    batch = std::min(batch, neta);
+    const int steps_cap = (int)std::min<int64_t>(max_iter, M1);
+    size_t need = 0;
+    scint_sv_sweep_multi_workspace_bytes(M1, M2, neta, batch, max_iter, ncs, &need);
+    if (workspace_bytes < need) { set_error("scint: sv_sweep_multi workspace too small"); return SCINT_E_WORKSPACE; }
+    hipStream_t stream = (hipStream_t)stream_;
+    // the slabs are laid out for the largest map of the call (M1 x M2 bounds every crop)
+    const SvSlab L = sv_slab(M1, M2, steps_cap);
+    Carver cv(workspace, workspace_bytes);
+    char* slabs = cv.take<char>(L.total * (size_t)batch);
+    SvJob* sv_dev = cv.take<SvJob>(batch);
+    LanczosJob* lj_dev = cv.take<LanczosJob>(batch);
+    ThinJob* tj_dev = cv.take<ThinJob>(batch);
+    ThinGeomDev* g_dev = cv.take<ThinGeomDev>(ncs);
+    int32_t* raise_dev = cv.take<int32_t>(batch);
+    int32_t* states_dev = cv.take<int32_t>(4 * batch);     // [batch][4]: done flag, steps (one read-back per check)
+    if (!cv.ok()) { set_error("scint: sv_sweep_multi workspace too small"); return SCINT_E_WORKSPACE; }
+    std::vector<ThinGeomDev> gh(ncs);
+    for (int64_t c = 0; c < ncs; ++c) gh[c] = to_dev(geoms[c]);
+    SCINT_HIP(hipMemcpyAsync(g_dev, gh.data(), sizeof(ThinGeomDev) * ncs, hipMemcpyHostToDevice, stream));
+    int32_t* flags = nullptr;
+    SCINT_HIP(hipHostMalloc(&flags, sizeof(int32_t) * 4 * (size_t)batch));
+    std::vector<SvJob> sv(batch);
+    std::vector<LanczosJob> lj(batch);
+    std::vector<ThinJob> tj(batch);
+    int32_t rc = SCINT_OK;
+    for (int64_t e0 = 0; e0 < neta && rc == SCINT_OK; e0 += batch) {
+        const int nj = (int)std::min<int64_t>(batch, neta - e0);
+        int64_t max_dom = 0, gmax = 1, n1b = 1;
+        bool cls_used[kSvClasses] = {};
+        int nmax_steps = 1;
+        for (int j = 0; j < nj; ++j) {
+            const int64_t e = e0 + j;
+            const int32_t* r = ranges + 6 * e;
+            char* s = slabs + L.total * (size_t)j;
+            ThinJob& t = tj[j];
+            const int c = cs_index[e];
+            t.cs = (const cplx*)cs_stack + (int64_t)c * cs_stride;
+            t.th1 = th1_stack + (int64_t)c * M1;
+            t.th2 = th2_stack + (int64_t)c * M2;
+            t.eta1 = etas1[e]; t.eta2 = etas2[e]; t.two_eta1 = 2 * etas1[e]; t.two_eta2 = 2 * etas2[e];
+            t.r0 = r[0]; t.n2 = r[1]; t.c0 = r[2]; t.n1 = r[3]; t.cut0 = r[4]; t.cut1 = r[5];
+            t.M1 = (int32_t)M1; t.M2 = (int32_t)M2; t.check = check[e] ? 1 : 0; t.geom = c;
+            t.out = (cplx*)(s + L.A);
+            t.raise = raise_dev + j;
+            max_dom = std::max<int64_t>(max_dom, t.check ? M1 * M2 : (int64_t)r[1] * r[3]);
+            SvJob& b = sv[j];
+            b.A = t.out; b.n1 = r[3]; b.n2 = r[1];
+            b.max_steps = (int)std::min<int64_t>(max_iter, std::max(r[3], 1));
+            b.R = sv_rows_per_group(std::max(r[1], 1));
+            b.G = (int)ceil_div(std::max(r[1], 1), b.R);
+            b.cls = sv_class(std::max(r[3], 1));
+            b.W[0] = (cplx*)(s + L.W0); b.W[1] = (cplx*)(s + L.W1); b.Q = (cplx*)(s + L.Q);
+            b.zpart = (cplx*)(s + L.zpart);
+            b.alpha = (double*)(s + L.alpha); b.beta = (double*)(s + L.beta);
+            b.apart = (double*)(s + L.apart); b.npart = (double*)(s + L.npart);
+            b.state = states_dev + 4 * j; b.lam = (double*)(s + L.lam);
+            b.status = (int32_t*)(s + L.status); b.iters = (int32_t*)(s + L.iters);
+            b.raise = t.raise;
+            gmax = std::max<int64_t>(gmax, b.G);
+            n1b = std::max<int64_t>(n1b, r[3]);
+            if (b.n1 >= 2 && b.n2 >= 1) { cls_used[b.cls] = true; nmax_steps = std::max(nmax_steps, b.max_steps); }
+            LanczosJob& l = lj[j];
+            l = LanczosJob{};
+            l.n = b.n1; l.max_steps = b.max_steps; l.qslots = 2;
+            l.alpha = b.alpha; l.beta = b.beta; l.apart = b.apart; l.npart = b.npart;
+            l.svec = nullptr; l.result = (double*)(s + L.result);
+            l.state = b.state; l.eig_out = b.lam; l.status_out = b.status; l.iters_out = b.iters;
+            l.tol = tol;
+        }
+        SCINT_HIP(hipMemsetAsync(raise_dev, 0, sizeof(int32_t) * nj, stream));
+        SCINT_HIP(hipMemcpyAsync(tj_dev, tj.data(), sizeof(ThinJob) * nj, hipMemcpyHostToDevice, stream));
+        SCINT_HIP(hipMemcpyAsync(sv_dev, sv.data(), sizeof(SvJob) * nj, hipMemcpyHostToDevice, stream));
+        SCINT_HIP(hipMemcpyAsync(lj_dev, lj.data(), sizeof(LanczosJob) * nj, hipMemcpyHostToDevice, stream));
+        const int slot = profiler().begin(kProfGather, stream);
+        rc = launch_thin_gather(tj_dev, g_dev, nj, max_dom, stream);
+        profiler().end(kProfGather, slot, stream);
+        if (rc != SCINT_OK) break;
+        const dim3 vgrid((unsigned)ceil_div(n1b, kVecBlock), (unsigned)nj);
+        hipLaunchKernelGGL(sv_init_kernel, vgrid, dim3(kVecBlock), 0, stream, sv_dev);
+        SCINT_LAUNCH_CHECK();
+        int step = 0, chunk = 16;
+        const int cap = nmax_steps;
+        bool any = false;
+        for (int k = 0; k < kSvClasses; ++k) any = any || cls_used[k];
+        while (any && step < cap) {
+            const int upto = std::min(cap, step + chunk);
+            for (; step < upto; ++step) {
+                const int ms = profiler().begin(kProfMatvec, stream);
+                for (int k = 0; k < kSvClasses; ++k)
+                    if (cls_used[k]) launch_sv_class(sv_dev, k, (unsigned)gmax, (unsigned)nj, step, stream);
+                profiler().end(kProfMatvec, ms, stream);
+                hipLaunchKernelGGL(sv_reduce_kernel, vgrid, dim3(kVecBlock), 0, stream, sv_dev, step);
+                hipLaunchKernelGGL(sv_update_kernel, vgrid, dim3(kVecBlock), 0, stream, sv_dev, step);
+            }
+            SCINT_LAUNCH_CHECK();
+            hipLaunchKernelGGL(lanczos_check_kernel, dim3((unsigned)nj), dim3(64), 0, stream, lj_dev, step,
+                               step >= cap ? 1 : 0);
+            SCINT_LAUNCH_CHECK();
+            SCINT_HIP(hipMemcpyAsync(flags, states_dev, sizeof(int32_t) * 4 * (size_t)nj, hipMemcpyDeviceToHost, stream));
+            SCINT_HIP(hipStreamSynchronize(stream));
+            if (profiler().enabled) profiler().collect();
+            bool all = true;
+            for (int j = 0; j < nj && all; ++j) all = flags[4 * j] != 0;
+            if (all) break;
+            chunk = 8;
+        }
+        hipLaunchKernelGGL(sv_finish_kernel, dim3((unsigned)ceil_div(nj, 64)), dim3(64), 0, stream, sv_dev, nj,
+                           sv_out + e0, status_out + e0, iters_out + e0);
+        SCINT_LAUNCH_CHECK();
+        SCINT_HIP(hipStreamSynchronize(stream));     // the job tables are rewritten for the next batch
+    }
+    (void)hipHostFree(flags);
+    return rc;
+}

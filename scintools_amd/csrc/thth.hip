@@ -1487,3 +1487,85 @@ extern "C" int32_t scint_sweep_keep(const double* th_cents, int64_t M, const dou
     SCINT_LAUNCH_CHECK();
     return SCINT_OK;
 }
+
+
+// ------------------------------------------------------------------------------
+// two_curve_map (ththmod.py:1557-1636): the rectangular theta-theta of the thin-screen search
+// ------------------------------------------------------------------------------
+// Grid (blocks, jobs); a block strides over its job's domain: the kept n2 x n1 block, or -- for a job whose grid can reach an
+// index NumPy rejects (check != 0) -- the full M2 x M1 grid, where only the kept points are written and every point is tested.
+namespace scint {
+__global__ void __launch_bounds__(256) thin_gather_kernel(const ThinJob* __restrict__ jobs, const ThinGeomDev* __restrict__ geoms) {
+    const ThinJob jb = jobs[blockIdx.y];
+    const ThinGeomDev g = geoms[jb.geom];
+    const int64_t cols = jb.check ? jb.M1 : jb.n1;
+    const int64_t rows = jb.check ? jb.M2 : jb.n2;
+    const int64_t dom = rows * cols;
+    bool raise = false;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < dom; t += (int64_t)gridDim.x * 256) {
+        const int64_t r = t / cols, c = t - r * cols;
+        const int64_t i2 = jb.check ? r : r + jb.r0, i1 = jb.check ? c : c + jb.c0;   // indices into the full grids
+        const int64_t kr = i2 - jb.r0, kc = i1 - jb.c0;                                   // position in the kept block
+        const bool kept = kr >= 0 && kr < jb.n2 && kc >= 0 && kc < jb.n1;
+        if (!kept && !jb.check) continue;
+        const double th1 = jb.th1[i1], th2 = jb.th2[i2];
+        cplx v = thin_value(jb.cs, g, jb.eta1, jb.eta2, jb.two_eta1, jb.two_eta2, th1, th2, &raise);
+        if (kept) {
+            if (kc >= jb.cut0 && kc < jb.cut1) v = mk(0.0, 0.0);
+            gstore(jb.out + kr * jb.n1 + kc, v);
+        }
+    }
+    if (raise) *jb.raise = 1;      // every writer stores the same value
+}
+
+int32_t launch_thin_gather(const ThinJob* jobs_dev, const ThinGeomDev* geoms_dev, int64_t njobs, int64_t max_domain,
+                           hipStream_t stream) {
+    if (njobs <= 0 || max_domain <= 0) return SCINT_OK;
+    const unsigned nb = (unsigned)std::min<int64_t>(ceil_div(max_domain, 256), 1024);
+    for (int64_t j0 = 0; j0 < njobs; j0 += 65535) {
+        const unsigned nj = (unsigned)std::min<int64_t>(65535, njobs - j0);
+        hipLaunchKernelGGL(thin_gather_kernel, dim3(nb, nj), dim3(256), 0, stream, jobs_dev + j0, geoms_dev);
+    }
+    SCINT_LAUNCH_CHECK();
+    return SCINT_OK;
+}
+}  // namespace scint
+
+extern "C" int32_t scint_two_curve_map_workspace_bytes(size_t* bytes) {
+    SCINT_REQUIRE(bytes != nullptr, "two_curve_map_workspace_bytes: null output");
+    *bytes = 1024;
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_two_curve_map(const scint_c128* cs, const scint_thin_geom* geom, const double* th1, int64_t M1,
+                                       const double* th2, int64_t M2, double eta1, double eta2, const int32_t* ranges,
+                                       int32_t check, scint_c128* thth_out, int32_t* raise_out, void* workspace,
+                                       size_t workspace_bytes, void* stream_) {
+    SCINT_REQUIRE(cs && geom && th1 && th2 && ranges && raise_out && workspace, "two_curve_map: null pointer");
+    SCINT_REQUIRE(workspace_bytes >= 1024, "two_curve_map: workspace too small");
+    SCINT_REQUIRE(M1 >= 1 && M2 >= 1 && M1 < (1 << 30) && M2 < (1 << 30), "two_curve_map: bad grid sizes");
+    SCINT_REQUIRE(geom->ntau >= 2 && geom->nfd >= 2 && geom->dtau > 0 && geom->dfd > 0,
+                  "two_curve_map: tau and fd must be increasing axes of at least two points");
+    const int32_t r0 = ranges[0], n2 = ranges[1], c0 = ranges[2], n1 = ranges[3], cut0 = ranges[4], cut1 = ranges[5];
+    SCINT_REQUIRE(r0 >= 0 && n2 >= 0 && r0 + (int64_t)n2 <= M2 && c0 >= 0 && n1 >= 0 && c0 + (int64_t)n1 <= M1,
+                  "two_curve_map: crop outside the grids");
+    SCINT_REQUIRE(cut0 >= 0 && cut0 <= cut1 && cut1 <= n1, "two_curve_map: centre cut outside the kept columns");
+    SCINT_REQUIRE(n2 == 0 || n1 == 0 || thth_out, "two_curve_map: null output");
+    hipStream_t stream = (hipStream_t)stream_;
+    ThinJob jb;
+    jb.cs = (const cplx*)cs; jb.th1 = th1; jb.th2 = th2;
+    jb.eta1 = eta1; jb.eta2 = eta2; jb.two_eta1 = 2 * eta1; jb.two_eta2 = 2 * eta2;
+    jb.r0 = r0; jb.n2 = n2; jb.c0 = c0; jb.n1 = n1; jb.cut0 = cut0; jb.cut1 = cut1;
+    jb.M1 = (int32_t)M1; jb.M2 = (int32_t)M2; jb.check = check ? 1 : 0; jb.geom = 0;
+    jb.out = (cplx*)thth_out; jb.raise = raise_out;
+    const ThinGeomDev g = to_dev(*geom);
+    char* base = (char*)workspace;
+    SCINT_HIP(hipMemsetAsync(raise_out, 0, sizeof(int32_t), stream));
+    SCINT_HIP(hipMemcpyAsync(base, &jb, sizeof(jb), hipMemcpyHostToDevice, stream));
+    SCINT_HIP(hipMemcpyAsync(base + 512, &g, sizeof(g), hipMemcpyHostToDevice, stream));
+    const int64_t dom = jb.check ? M1 * M2 : (int64_t)n1 * n2;
+    int32_t rc = launch_thin_gather((const ThinJob*)base, (const ThinGeomDev*)(base + 512), 1, dom, stream);
+    if (rc != SCINT_OK) return rc;
+    SCINT_HIP(hipStreamSynchronize(stream));     // the job table lives in the caller's workspace
+    return SCINT_OK;
+}

@@ -97,6 +97,66 @@ __device__ inline int64_t thth_offset(const GeomDev& g, double eta, double th_i,
     return tau_inv * g.nfd + fd_inv;
 }
 
+// ---- rectangular two-curvature map of the thin-screen search (two_curve_map, ththmod.py:1557-1636) ----------------------
+// Not thth_map with a second grid: the indices are taken from tau[1] and fd[1] (not tau[0], fd[0]), the delay operand is
+// (eta1 th1^2 - eta2 th2^2) in that order, the kept points are 0 < tau_inv < ntau - 1 and fd_inv < nfd - 1 (no lower bound on
+// fd_inv: NumPy's fancy index wraps a negative one, and raises IndexError below -nfd), and the weight is
+// sqrt(|2 eta1 th1 - 2 eta2 th2|).  Rows are theta2 (arclets), columns theta1 (main arc).
+struct ThinGeomDev {
+    int64_t ntau, nfd;
+    double tau1, dtau, half_dtau;  // tau[1], diff(tau).mean(), dtau/2
+    double fd1, dfd, half_dfd;     // fd[1],  diff(fd).mean(),  dfd/2
+};
+inline ThinGeomDev to_dev(const scint_thin_geom& g) {
+    ThinGeomDev d;
+    d.ntau = g.ntau; d.nfd = g.nfd;
+    d.tau1 = g.tau1; d.dtau = g.dtau; d.half_dtau = g.dtau / 2;
+    d.fd1 = g.fd1; d.dfd = g.dfd; d.half_dfd = g.dfd / 2;
+    return d;
+}
+
+// Linear offset into CS of the pixel feeding (theta1, theta2); -1 outside `pnts` (value 0), -2 where NumPy would raise.
+// The floors stay in float64 for the range tests (a NaN operand fails them, as NumPy's INT_MIN from astype(int) does).
+__device__ inline int64_t thin_offset(const ThinGeomDev& g, double eta1, double eta2, double th1, double th2) {
+    const double a_tau = ((eta1 * (th1 * th1) - eta2 * (th2 * th2)) - g.tau1) + g.half_dtau;
+    const double a_fd = ((th1 - th2) - g.fd1) + g.half_dfd;
+    const double ti = floor_div_exact(a_tau, g.dtau);
+    const double fi = floor_div_exact(a_fd, g.dfd);
+    if (!(ti > 0.0 && ti < (double)(g.ntau - 1) && fi < (double)(g.nfd - 1))) return -1;
+    int64_t f = (int64_t)fi;
+    if (fi < 0.0) {
+        if (fi < -(double)g.nfd) return -2;
+        f += g.nfd;
+    }
+    return (int64_t)ti * g.nfd + f;
+}
+
+__device__ inline cplx thin_value(const cplx* __restrict__ cs, const ThinGeomDev& g, double eta1, double eta2,
+                                  double two_eta1, double two_eta2, double th1, double th2, bool* raise) {
+    const int64_t o = thin_offset(g, eta1, eta2, th1, th2);
+    if (o == -2) *raise = true;
+    if (o < 0) return mk(0.0, 0.0);
+    const cplx v = cs[o];
+    const double w = sqrt(fabs(two_eta1 * th1 - two_eta2 * th2));
+    return mk(v.x * w, v.y * w);
+}
+
+// One rectangular map to build.  Kept rows [r0, r0 + n2) of the theta2 centres, kept columns [c0, c0 + n1) of the theta1
+// centres, of which the reduced columns [cut0, cut1) are written as zero (singularvalue_calc's centre cut, ththmod.py:509).
+// check != 0: also scan the FULL M2 x M1 grid for an index NumPy would reject (the host proves it unreachable otherwise) and
+// set *raise.
+struct ThinJob {
+    const cplx* cs;
+    const double* th1;
+    const double* th2;
+    double eta1, eta2, two_eta1, two_eta2;
+    int32_t r0, n2, c0, n1, cut0, cut1, M1, M2, check, geom;
+    cplx* out;                 // [n2][n1]
+    int32_t* raise;            // device word, 0 on entry
+};
+int32_t launch_thin_gather(const ThinJob* jobs_dev, const ThinGeomDev* geoms_dev, int64_t njobs, int64_t max_domain,
+                           hipStream_t stream);
+
 // One theta-theta matrix to build: curvature, crop and destination.
 struct GatherJob {
     double eta, two_eta;     // eta and 2*eta (ththmod.py:95, 107)

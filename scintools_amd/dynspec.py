@@ -294,15 +294,15 @@ class Dynspec:
         """Set the theta-theta search parameters (dynspec.py:1348-1537).
 
         Same keywords as the reference: cwf, cwt, fref, eta_min, eta_max, nedge, edges_lim,
-        tau_lim, tau_mask (bare numbers in s**3 / mHz / us / MHz, or astropy Quantities).
+        tau_lim, tau_mask, and for ``fitting_proc='thin'`` arclet_lim (default: edges_lim) and
+        center_cut (default 0) (bare numbers in s**3 / mHz / us / MHz, or astropy Quantities).
         Without ``eta_min`` / ``eta_max`` the bounds come from ``fit_arc(lamsteps=True)`` on
-        the secondary spectrum, as in the reference (dynspec.py:1458-1473).  The 'thin'
-        procedure (rectangular theta-theta + SVD) is out of scope.
+        the secondary spectrum, as in the reference (dynspec.py:1458-1473).  'thin' models only
+        the arclet apexes: a rectangular theta-theta per curvature and its largest singular value
+        (ththmod.two_curve_map / singularvalue_calc); its edges reach fd.max(), not fd.max()/2.
         """
         fitting_procs = ['standard', 'thin', 'incoherent']
         assert fitting_proc in fitting_procs, f'fitting_proc must be one of {fitting_procs}'
-        if fitting_proc == 'thin':
-            raise NotImplementedError("fitting_proc='thin' (two-curvature SVD) is outside the hot path")
         val = lambda key, unit, name: float(units.strip(kwargs[key], name, unit, warn=False))
         self.thetatheta_proc = fitting_proc
         self.npad = npad
@@ -343,7 +343,10 @@ class Dynspec:
                 self.eta_max = min((self.eta_max, eta_hough + err_hough))
         l0, l1 = np.log10(self.eta_min), np.log10(self.eta_max)
         self.neta = int(1 + (l1 - l0) / np.log10(1 + self.fw / 10))     # dynspec.py:1478
-        fd_cut = (fd.max() / 2) * (self.fref / self.freqs.max())
+        if fitting_proc == 'thin':                                # dynspec.py:1480-1483
+            fd_cut = fd.max() * (self.fref / self.freqs.max())
+        else:
+            fd_cut = (fd.max() / 2) * (self.fref / self.freqs.max())
         edges_lim = min((val('edges_lim', 'mHz', 'edges limit'), fd_cut)) if 'edges_lim' in kwargs else fd_cut
         if tau_lim is not None:
             edges_lim = min((edges_lim, np.sqrt(tau_lim / self.eta_max)))
@@ -356,6 +359,9 @@ class Dynspec:
                 * (self.freqs.min() / self.fref)
             if units.HAVE_ASTROPY:
                 self.edges = np.asarray(getattr(self.edges, "value", self.edges))
+        if fitting_proc == 'thin':                                # dynspec.py:1505-1516
+            self.arclet_lim = val('arclet_lim', 'mHz', 'Arclet Limit') if 'arclet_lim' in kwargs else edges_lim
+            self.center_cut = val('center_cut', 'mHz', 'Central Cut') if 'center_cut' in kwargs else 0
         self.thth_tau_mask = val('tau_mask', 'us', 'tau_mask') if 'tau_mask' in kwargs else 0.0
         if verbose:
             print("\n\t THETA-THETA PROPERTIES\n")
@@ -399,7 +405,12 @@ class Dynspec:
                                      self.thetatheta_proc != 'incoherent', pad_value=0.0)
         etas = self._chunk_etas(freq2)
         edges = self.edges * (freq2.mean() / self.fref)
-        eigs = thth.eval_sweep(cs, tau, fd, etas, edges)
+        if self.thetatheta_proc == 'thin':
+            # scaled to the chunk BEFORE the arclet filter here (dynspec.py:1590-1596), after it in fit_thetatheta
+            eigs = thth.sv_sweep_multi(cs.unsqueeze(0), [(tau, fd, edges, edges[np.abs(edges) < self.arclet_lim])], [etas],
+                                       self.center_cut)[0]
+        else:
+            eigs = thth.eval_sweep(cs, tau, fd, etas, edges)
         _, _, popt = thth.fit_eig_peak(etas, eigs, self.fw)
         if arrays:
             return etas, eigs, popt
@@ -409,6 +420,7 @@ class Dynspec:
         Chunks are grouped so that a stack of conjugate spectra stays below ~8 GiB; each group is
         one ``eval_sweep_multi`` call (all (chunk, eta) pairs batched together)."""
         coher = (self.thetatheta_proc != 'incoherent')
+        thin = self.thetatheta_proc == 'thin'
         R, C = (self.npad + 1) * self.cwf, (self.npad + 1) * self.cwt
         per_group = max(1, int((8 << 30) // (16 * R * C)))
         rows = np.full((len(group_all), 2 + self.neta), np.nan)
@@ -429,13 +441,30 @@ class Dynspec:
                 etas_list.append(etas)
             d_t = thth.to_device(d_all, torch.float64)
             for k in range(len(group)):
-                thth.conjugate_spectrum(d_t[k], self.npad, grids[k][0], self.thth_tau_mask, coher, pad_value=pads[k], out=stack[k])
-            eig_list = thth.eval_sweep_multi(stack, grids, etas_list)
+                # the thin search pads with the mean too but applies no delay mask, even when one was set (dynspec.py:1689-1719)
+                thth.conjugate_spectrum(d_t[k], self.npad, None if thin else grids[k][0], self.thth_tau_mask, coher,
+                                        pad_value=pads[k], out=stack[k])
+            if thin:
+                arclet = self._arclet_edges()
+                eig_list = thth.sv_sweep_multi(stack, [g + (arclet * (self.freqs[self._chunk(cf, ct)[0]].mean() / self.fref),)
+                                                       for g, (cf, ct) in zip(grids, group)], etas_list, self.center_cut)
+            else:
+                eig_list = thth.eval_sweep_multi(stack, grids, etas_list)
             for k, (etas, eigs) in enumerate(zip(etas_list, eig_list)):
                 eta_fit, eta_sig, _ = thth.fit_eig_peak(etas, eigs, self.fw)   # ththmod.py:814-859
                 rows[g0 + k, 0], rows[g0 + k, 1] = eta_fit, eta_sig
                 rows[g0 + k, 2:] = eigs
         return rows
+
+    def _arclet_edges(self):
+        """fit_thetatheta's arclet grid: self.edges filtered by arclet_lim BEFORE the scaling to a chunk (dynspec.py:1706-1709)."""
+        return self.edges[np.abs(self.edges) < self.arclet_lim]
+
+    def _search_params_thin(self, cf, ct, verbose=False):
+        """The 13-element parameter list the reference hands to ``single_search_thin`` (dynspec.py:1689-1709), plain floats."""
+        p = self._search_params(cf, ct, verbose)
+        freq2 = p[1]
+        return p[:10] + [verbose, self._arclet_edges() * (freq2.mean() / self.fref), self.center_cut]
 
     def _search_params(self, cf, ct, verbose=False):
         """The 12-element parameter list the reference hands to ``single_search`` for fitting
@@ -459,7 +488,7 @@ class Dynspec:
             and all (chunk, eta) pairs run as ONE continuously batched sweep on this GPU; under an
             initialised ``torch.distributed`` group the chunks are dealt round-robin to the ranks
             (one GPU each) and the fitted curvatures are all-gathered (``sweep.sharded_chunks``);
-          * ``pool`` given: exactly the reference's ``pool.map(thth.single_search, pars)``
+          * ``pool`` given: exactly the reference's ``pool.map(thth.single_search, pars)`` (``single_search_thin`` for 'thin')
             (dynspec.py:1715-1719) -- with ``sweep.gpu_pool(n)`` every worker process drives its
             own GPU.
         """
@@ -478,7 +507,10 @@ class Dynspec:
             self.f0s[cf] = self.freqs[fs].mean()
             self.t0s[ct] = self.times[ts].mean()
         if pool is not None:
-            res = pool.map(thth.single_search, [self._search_params(cf, ct, verbose) for cf, ct in chunks])
+            if getattr(self, 'thetatheta_proc', 'standard') == 'thin':
+                res = pool.map(thth.single_search_thin, [self._search_params_thin(cf, ct, verbose) for cf, ct in chunks])
+            else:
+                res = pool.map(thth.single_search, [self._search_params(cf, ct, verbose) for cf, ct in chunks])
             for (cf, ct), r in zip(chunks, res):
                 # with astropy present single_search returns Quantities (s**3): strip before the
                 # plain-float arrays take them (a NumPy scalar assignment of a Quantity raises)

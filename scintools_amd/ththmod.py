@@ -17,6 +17,10 @@ chisq_sweep        (a loop of chisq_calc) scint_chisq_sweep
 Eval_calc          ththmod.py:371-401     scint_eval_sweep (one eta)
 single_search      ththmod.py:715-895     scint_cs + scint_eval_sweep (+ SciPy fit)
 eval_sweep         (the loop :788-799)    scint_eval_sweep
+two_curve_map      ththmod.py:1557-1636   scint_two_curve_map
+singularvalue_calc ththmod.py:496-513     scint_sv_sweep_multi (one map)
+single_search_thin ththmod.py:516-712     scint_cs + scint_sv_sweep_multi (+ SciPy fit)
+sv_sweep_multi     (fit_thetatheta thin)  scint_sv_sweep_multi
 =================  =====================  ========================================
 
 ``tau, fd, eta, edges`` may be bare numbers (us, mHz, s**3, mHz) or, when astropy
@@ -1410,3 +1414,263 @@ def calc_asymmetry(params):
         print(exc, flush=True)
         asymm = np.nan
     return (asymm, idx_f, idx_t)
+
+
+# ----------------------------------------------------------------------------
+# thin-screen curvature search (fitting_proc='thin', ththmod.py:496-712 and 1557-1636)
+# ----------------------------------------------------------------------------
+def _thin_geom(tau, fd):
+    """scint_thin_geom of (tau, fd): the reference's own expressions (ththmod.py:1593-1604)."""
+    g = _lib.ThinGeom()
+    g.ntau, g.nfd = int(tau.shape[0]), int(fd.shape[0])
+    g.tau1, g.dtau = float(tau[1]), float(np.diff(tau).mean())
+    g.fd1, g.dfd = float(fd[1]), float(np.diff(fd).mean())
+    return g
+
+
+def _thin_centres(edges):
+    return (edges[1:] + edges[:-1]) / 2                     # ththmod.py:1583-1584: no re-centring
+
+
+def _run(mask):
+    """(first, count) of a boolean mask that must be one run of True."""
+    idx = np.nonzero(mask)[0]
+    if idx.size == 0:
+        return 0, 0
+    if idx[-1] - idx[0] + 1 != idx.size:
+        raise ValueError("thin theta-theta: a crop or centre cut is not one run of centres (edges must be monotonic)")
+    return int(idx[0]), int(idx.size)
+
+
+def _reduced_edges(edges, pnts):
+    """edges_red of two_curve_map (ththmod.py:1625-1630); raises ValueError on an empty crop, as the reference's .max() does."""
+    er = np.zeros(pnts[pnts].shape[0] + 1)
+    er[:-1] = edges[:-1][pnts]
+    er[-1] = edges[1:][pnts].max()
+    return er
+
+
+def _thin_crop(tau_max, edges1, edges2, eta1, eta2, center_cut):
+    """ranges [r0, n2, c0, n1, cut0, cut1] of one map and its reduced edges, with the reference's masks:
+    |centre| < sqrt(tau.max() / eta) on each axis (ththmod.py:1621-1624) and |reduced centre| < centerCut (:509)."""
+    pnts_1 = np.abs(_thin_centres(edges1)) < np.sqrt(tau_max / eta1)
+    pnts_2 = np.abs(_thin_centres(edges2)) < np.sqrt(tau_max / eta2)
+    er1, er2 = _reduced_edges(edges1, pnts_1), _reduced_edges(edges2, pnts_2)
+    c0, n1 = _run(pnts_1)
+    r0, n2 = _run(pnts_2)
+    cut0, ncut = _run(np.abs(_thin_centres(er1)) < center_cut)
+    return np.array([r0, n2, c0, n1, cut0, cut0 + ncut], dtype=np.int32), er1, er2
+
+
+def _thin_check(geom, th1, th2):
+    """1 if some point of the grid can reach fd_inv < -nfd (NumPy's IndexError, ththmod.py:1612): fd_inv is monotone in
+    th1 - th2, so its smallest value is at (min th1, max th2)."""
+    if th1.size == 0 or th2.size == 0:
+        return 0
+    a = ((th1.min() - th2.max()) - geom.fd1) + geom.dfd / 2
+    return int(np.floor_divide(a, geom.dfd) < -geom.nfd or not np.isfinite(a))
+
+
+def _thin_cs_dev(CS, tau, fd):
+    t = to_device(CS, torch.complex128)
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    if tuple(t.shape[1:]) != (tau.shape[0], fd.shape[0]):
+        raise ValueError(f"CS shape {tuple(t.shape[1:])} does not match (len(tau), len(fd)) = ({tau.shape[0]}, {fd.shape[0]})")
+    return t.contiguous()
+
+
+def two_curve_map(CS, tau, fd, eta1, edges1, eta2, edges2):
+    """Rectangular theta-theta for arclets of another curvature (ththmod.py:1557-1636): returns
+    (thth_red[n2, n1], edges_red1, edges_red2) -- rows theta2 (edges2), columns theta1 (edges1) -- with the reference's index
+    quirks (tau[1] / fd[1] origins, the negative-Doppler wrap, IndexError below -nfd)."""
+    lib = _lib.load()
+    require_gpu()
+    tau_v = units.strip(tau, "tau", "us", warn=False)
+    fd_v = units.strip(fd, "fd", "mHz", warn=False)
+    e1 = np.array(units.strip(edges1, "edges1", "mHz", warn=False), dtype=float)
+    e2 = np.array(units.strip(edges2, "edges2", "mHz", warn=False), dtype=float)
+    eta1_v, eta2_v = _eta_float(eta1), _eta_float(eta2)
+    geom = _thin_geom(tau_v, fd_v)
+    th1, th2 = _thin_centres(e1), _thin_centres(e2)
+    if th1.size < 1 or th2.size < 1:
+        raise ValueError("two_curve_map: edges need at least two points")
+    rng, er1, er2 = _thin_crop(tau_v.max(), e1, e2, eta1_v, eta2_v, 0.0)
+    cs_t = _thin_cs_dev(CS, tau_v, fd_v)
+    n2, n1 = int(rng[1]), int(rng[3])
+    out = empty((max(n2, 1), max(n1, 1)), torch.complex128)
+    flag = torch.zeros((1,), dtype=torch.int32, device=out.device)
+    need = ctypes.c_size_t()
+    _lib.check(lib.scint_two_curve_map_workspace_bytes(ctypes.byref(need)), "two_curve_map_workspace_bytes")
+    ws = workspace.get(need.value)
+    th1_t, th2_t = to_device(th1, torch.float64), to_device(th2, torch.float64)
+    rc = lib.scint_two_curve_map(ptr(cs_t), ctypes.byref(geom), ptr(th1_t), th1.size, ptr(th2_t), th2.size, eta1_v, eta2_v,
+                                 rng.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _thin_check(geom, th1, th2),
+                                 ptr(out), ptr(flag), ptr(ws), ws.numel(), stream_ptr())
+    _lib.check(rc, "scint_two_curve_map")
+    if int(flag.cpu()[0]):
+        raise IndexError("two_curve_map: a Doppler index below -len(fd) (NumPy's fancy index raises here, ththmod.py:1612)")
+    red = out[:n2, :n1].cpu().numpy()
+    return red, units.attach(er1, "mHz"), units.attach(er2, "mHz")
+
+
+def _sv_run(cs_t, geoms, th1_stack, th2_stack, cs_index, ranges, checks, etas1, etas2, tol, max_iter, batch):
+    """scint_sv_sweep_multi on prepared inputs: (sv[neta], status[neta], iters[neta], batch)."""
+    lib = _lib.load()
+    ncs, M1, M2 = len(geoms), int(th1_stack.shape[1]), int(th2_stack.shape[1])
+    neta = int(etas1.shape[0])
+    _check_sweep_cs(geoms[0].ntau, geoms[0].nfd)
+    if batch is None:
+        per = 16 * M1 * M2 + 96 * M1 + 16 * M1 * -(-M2 // max(4, -(-M2 // 256))) + 16 * max_iter + 4096
+        batch = int(max(1, min(neta, 8192, DEFAULT_BATCH_BYTES // per)))
+    need = ctypes.c_size_t()
+    _lib.check(lib.scint_sv_sweep_multi_workspace_bytes(M1, M2, neta, batch, max_iter, ncs, ctypes.byref(need)),
+               "sv_sweep_multi_workspace_bytes")
+    ws = workspace.get(need.value)
+    sv_t = empty((neta,), torch.float64)
+    st_t = empty((2, neta), torch.int32)
+    g_arr = (_lib.ThinGeom * ncs)(*geoms)
+    ci = np.ascontiguousarray(cs_index, dtype=np.int32)
+    rg = np.ascontiguousarray(ranges, dtype=np.int32)
+    ck = np.ascontiguousarray(checks, dtype=np.int32)
+    e1 = np.ascontiguousarray(etas1, dtype=np.float64)
+    e2 = np.ascontiguousarray(etas2, dtype=np.float64)
+    P = ctypes.POINTER
+    rc = lib.scint_sv_sweep_multi(ptr(cs_t), ncs, int(cs_t.shape[1] * cs_t.shape[2]), ci.ctypes.data_as(P(ctypes.c_int32)),
+                                  g_arr, ptr(th1_stack), M1, ptr(th2_stack), M2, rg.ctypes.data_as(P(ctypes.c_int32)),
+                                  ck.ctypes.data_as(P(ctypes.c_int32)), e1.ctypes.data_as(P(ctypes.c_double)),
+                                  e2.ctypes.data_as(P(ctypes.c_double)), neta, tol, max_iter, batch, ptr(sv_t),
+                                  ptr(st_t[0]), ptr(st_t[1]), ptr(ws), ws.numel(), stream_ptr())
+    _lib.check(rc, "scint_sv_sweep_multi")
+    st = st_t.cpu().numpy()
+    return sv_t.cpu().numpy(), st[0].copy(), st[1].copy(), batch
+
+
+def _thin_ranges(tau_max, edges1, edges2, etas, center_cut):
+    """ranges[neta, 6] of one chunk's curvatures (eta1 = eta2 = eta); an empty crop gets n = 0 (status EMPTY -> NaN, where the
+    reference's .max() of an empty selection raises inside single_search_thin's try)."""
+    th1, th2 = _thin_centres(edges1), _thin_centres(edges2)
+    out = np.zeros((etas.shape[0], 6), dtype=np.int32)
+    a1, a2 = np.abs(th1), np.abs(th2)
+    asc = th1.size > 0 and np.all(np.diff(edges1) > 0)
+    cutc = a1 < center_cut
+    for k, eta in enumerate(etas):
+        if asc:   # ascending edges: the reduced centres are th1[c0:c0 + n1], bit for bit (same two operands per centre)
+            p1 = a1 < np.sqrt(tau_max / eta)
+            p2 = a2 < np.sqrt(tau_max / eta)
+            c0, n1 = _run(p1)
+            r0, n2 = _run(p2)
+            if n1 == 0 or n2 == 0:
+                continue
+            cut0, ncut = _run(cutc[c0:c0 + n1])
+            out[k] = (r0, n2, c0, n1, cut0, cut0 + ncut)
+        else:
+            try:
+                out[k] = _thin_crop(tau_max, edges1, edges2, eta, eta, center_cut)[0]
+            except ValueError as err:
+                if "one run" in str(err):
+                    raise
+    return out
+
+
+def sv_sweep_multi(cs_stack, grids, etas_list, center_cut=0.0, tol=DEFAULT_TOL, max_iter=DEFAULT_MAX_ITER, batch=None,
+                   return_info=False):
+    """Singular-value curves of MANY chunks in one batched device call -- the chunk loop of Dynspec.fit_thetatheta with
+    fitting_proc='thin' (dynspec.py:1681-1719), each chunk's curvature loop being single_search_thin's (ththmod.py:588-643).
+
+    cs_stack: [nchunk, ntau, nfd] complex128 (device tensor or array); grids: one (tau, fd, edges, edges_arclet) per chunk (all
+    spectra one shape, all edges one length, all arclet edges one length); etas_list: per-chunk curvatures (main arc = arclets);
+    center_cut in mHz.  Returns a list of sigma_1 arrays, NaN where single_search_thin would have caught an exception."""
+    cs_t = _thin_cs_dev(cs_stack, *(units.strip(grids[0][i], n, k, warn=False) for i, n, k in ((0, "tau", "us"), (1, "fd", "mHz"))))
+    ncs = len(grids)
+    if cs_t.shape[0] != ncs:
+        raise ValueError("cs_stack must be [nchunk, ntau, nfd] with one spectrum per grid")
+    cut = float(units.strip(center_cut, "Center Cut", "mHz", warn=False))
+    geoms, th1s, th2s, ranges, checks, etas_all, cs_index = [], [], [], [], [], [], []
+    for c, ((tau, fd, edges, arclet), et) in enumerate(zip(grids, etas_list)):
+        tau_v, fd_v = units.strip(tau, "tau", "us", warn=False), units.strip(fd, "fd", "mHz", warn=False)
+        e1 = np.array(units.strip(edges, "edges", "mHz", warn=False), dtype=float)
+        e2 = np.array(units.strip(arclet, "edgesArclet", "mHz", warn=False), dtype=float)
+        et = np.atleast_1d(units.strip(et, "etas", "s3", warn=False)).astype(float)
+        g = _thin_geom(tau_v, fd_v)
+        th1, th2 = _thin_centres(e1), _thin_centres(e2)
+        if (g.ntau, g.nfd) != tuple(cs_t.shape[1:]):
+            raise ValueError("all chunks must share the CS shape")
+        if th1s and (th1.size != th1s[0].size or th2.size != th2s[0].size):
+            raise ValueError("all chunks must share the number of edges and of arclet edges")
+        geoms.append(g)
+        th1s.append(th1)
+        th2s.append(th2)
+        ranges.append(_thin_ranges(tau_v.max(), e1, e2, et, cut))
+        checks.append(np.full(et.shape[0], _thin_check(g, th1, th2), dtype=np.int32))
+        etas_all.append(et)
+        cs_index.append(np.full(et.shape[0], c, dtype=np.int32))
+    M1, M2 = th1s[0].size, th2s[0].size
+    etas_v = np.concatenate(etas_all)
+    if M1 < 1 or M2 < 1:          # fewer than two edges on an axis: every curvature fails, as the reference's do
+        sv, st, it = np.full(etas_v.shape, np.nan), np.full(etas_v.shape, _lib.SCINT_E_EMPTY), np.zeros(etas_v.shape, int)
+    else:
+        th1_t = to_device(np.stack(th1s), torch.float64)
+        th2_t = to_device(np.stack(th2s), torch.float64)
+        sv, st, it, batch = _sv_run(cs_t, geoms, th1_t, th2_t, np.concatenate(cs_index), np.concatenate(ranges),
+                                    np.concatenate(checks), etas_v, etas_v, tol, max_iter, batch)
+    sv[st != 0] = np.nan          # NOCONV / EMPTY / NONFINITE / would-raise -> NaN (single_search_thin's except, :624-629)
+    bounds = np.cumsum([0] + [e.shape[0] for e in etas_all])
+    out = [sv[bounds[i]:bounds[i + 1]] for i in range(ncs)]
+    if return_info:
+        return out, {"status": st, "iters": it, "ranges": np.concatenate(ranges), "batch": batch}
+    return out
+
+
+def singularvalue_calc(CS, tau, fd, eta, edges, etaArclet, edgesArclet, centerCut):
+    """Largest singular value of the centre-cut two-curvature map (ththmod.py:496-513).  Raises where the reference raises:
+    ValueError for an empty crop, IndexError where the map's Doppler index is out of NumPy's range."""
+    tau_v = units.strip(tau, "tau", "us", warn=False)
+    fd_v = units.strip(fd, "fd", "mHz", warn=False)
+    e1 = np.array(units.strip(edges, "edges", "mHz", warn=False), dtype=float)
+    e2 = np.array(units.strip(edgesArclet, "edgesArclet", "mHz", warn=False), dtype=float)
+    eta1_v, eta2_v = _eta_float(eta), _eta_float(etaArclet)
+    cut = float(units.strip(centerCut, "Center Cut", "mHz", warn=False))
+    rng, _, _ = _thin_crop(tau_v.max(), e1, e2, eta1_v, eta2_v, cut)       # ValueError on an empty crop, as the reference
+    cs_t = _thin_cs_dev(CS, tau_v, fd_v)
+    geom = _thin_geom(tau_v, fd_v)
+    th1, th2 = _thin_centres(e1), _thin_centres(e2)
+    sv, st, _, _ = _sv_run(cs_t, [geom], to_device(th1[None, :], torch.float64), to_device(th2[None, :], torch.float64),
+                           np.zeros(1, np.int32), rng[None, :], np.array([_thin_check(geom, th1, th2)], np.int32),
+                           np.array([eta1_v]), np.array([eta2_v]), DEFAULT_TOL, DEFAULT_MAX_ITER, 1)
+    if st[0] == _lib.SCINT_E_ARG:
+        raise IndexError("singularvalue_calc: a Doppler index below -len(fd) (NumPy's fancy index raises, ththmod.py:1612)")
+    if st[0] == _lib.SCINT_E_NONFINITE:
+        raise np.linalg.LinAlgError("singularvalue_calc: non-finite theta-theta (SVD did not converge)")
+    if st[0] != 0:
+        raise ArithmeticError(f"singularvalue_calc failed (status {int(st[0])})")
+    return float(sv[0])
+
+
+def single_search_thin(params):
+    """Thin-screen curvature search for one chunk (ththmod.py:516-712).
+
+    params = [dspec2, freq, time, etas, edges, name, plot, fw, npad, coher, verbose, edgesArclet, centerCut] as in the
+    reference (padding with dspec2.mean(), no delay mask).  Plotting is not supported (`plot=True` only warns).  Returns
+    (eta_fit, eta_sig, freq.mean(), time.mean(), eigs) with eigs the singular values of the curvatures that did not fail."""
+    (dspec2, freq, time, etas, edges, name, plot, fw, npad, coher, verbose, edgesArclet, centerCut) = params
+    time_v = units.strip(time, "time", "s", warn=False)
+    freq_v = units.strip(freq, "freq", "MHz", warn=False)
+    etas_v = np.atleast_1d(units.strip(etas, "etas", "s3", warn=False)).astype(float)
+    edges_v = units.strip(edges, "edges", "mHz", warn=False)
+    fd = fft_axis(time_v, 1000.0, npad)          # ththmod.py:582
+    tau = fft_axis(freq_v, 1.0, npad)            # ththmod.py:583
+    # coherent: CS; incoherent: |CS|^2 (ththmod.py:630-631) -- scint_cs's incoherent mode is |CS|, so square it here
+    cs_t = conjugate_spectrum(dspec2, npad, coher=True)
+    if not coher:
+        cs_t = (cs_t.abs() ** 2).to(torch.complex128)
+    eigs = sv_sweep_multi(cs_t.unsqueeze(0), [(tau, fd, edges_v, edgesArclet)], [etas_v], centerCut)[0]
+    eta_fit, eta_sig, _ = fit_eig_peak(etas_v, eigs, fw)
+    if plot:
+        warnings.warn("scintools_amd.single_search_thin does not plot")
+    if verbose:
+        print(f"Chunk completed (eta = {eta_fit} +- {eta_sig} at {freq_v.mean()})", flush=True)
+    if np.isfinite(eta_fit):
+        eta_fit, eta_sig = units.attach(eta_fit, "s3"), units.attach(eta_sig, "s3")
+    return (eta_fit, eta_sig, units.attach(freq_v.mean(), "MHz"), units.attach(time_v.mean(), "s"),
+            eigs[np.isfinite(eigs)])
