@@ -413,28 +413,34 @@ __global__ void __launch_bounds__(256) rev_count_kernel(const double* __restrict
         if (bx >= 0 && by >= 0) atomicAdd(cnt + by * g.nfd + bx, 1u);
     }
 }
-constexpr int kRowRun = 8;     // positions looked at either side for the same pixel (a Doppler bin holds two or three centres)
 constexpr int kTailGroup = 8;  // chunks of a class whose back-maps and zero-fills go in one launch (their images side by side)
 struct TailMembers { int32_t k[kTailGroup]; };
-// one workgroup per chunk of the class: pixel and weight of every j, then each pixel's first j adds its run and writes it
+// One workgroup per chunk of the class: Doppler bin, pixel and weight of every j, then each pixel's first j adds all of the
+// pixel's weights and writes it.  For the fixed i, fl(tj - ti) is monotone in j, so the j of one Doppler bin form ONE contiguous
+// run (any j of a pixel lies in the run of its column) -- but the pixels within a run need not be: in the bin that holds tj = ti,
+// eta (tj^2 - ti^2) changes sign and the pixel of -x recurs after those of smaller |x|.  So a j is its pixel's head if no earlier j
+// of its run has the pixel, and the head adds every later j of the run that has it, in increasing j (NumPy's bincount order): one
+// writer per pixel, no float atomics.  The runs are a few centres on the product's grids; a dense grid (a user nedge, npad = 0)
+// makes them tens or hundreds long, and the walk grows with the run, not with N.
 __global__ void __launch_bounds__(256) rev_row_kernel(const cplx* __restrict__ rows, const double* __restrict__ th_red, int64_t M,
                                                       TailMembers members, int N, double eta, GeomDev g,
                                                       const uint32_t* __restrict__ cnt, cplx* __restrict__ recov_all, int64_t centre,
-                                                      int64_t* __restrict__ pix_all, cplx* __restrict__ val_all) {
+                                                      int64_t* __restrict__ pix_all, cplx* __restrict__ val_all, int32_t* __restrict__ col_all) {
     const int k = members.k[blockIdx.x];
     const cplx* __restrict__ row = rows + (int64_t)k * M;
     const double* __restrict__ th = th_red + (int64_t)k * M;
     cplx* __restrict__ recov = recov_all + (int64_t)blockIdx.x * g.ntau * g.nfd;
     int64_t* __restrict__ pix = pix_all + (int64_t)blockIdx.x * M;
     cplx* __restrict__ val = val_all + (int64_t)blockIdx.x * M;
+    int32_t* __restrict__ col = col_all + (int64_t)blockIdx.x * M;
     const int i = N / 2;
     const double ti = th[i], two_eta = 2 * eta;
     for (int j = threadIdx.x; j < N; j += 256) {
         int64_t o = -1;
         cplx v = mk(0.0, 0.0);
+        const double tj = th[j];
+        const int64_t bx = hist_bin(tj - ti, g.fd0, g.fd1_step, g.nfd);             // (also for j = i: its run continues past it)
         if (j != i) {
-            const double tj = th[j];
-            const int64_t bx = hist_bin(tj - ti, g.fd0, g.fd1_step, g.nfd);
             const int64_t by = hist_bin(eta * (tj * tj - ti * ti), g.tau0, g.tau1_step, g.ntau);
             if (bx >= 0 && by >= 0) {
                 o = by * g.nfd + bx;
@@ -442,18 +448,20 @@ __global__ void __launch_bounds__(256) rev_row_kernel(const cplx* __restrict__ r
                 v = mk(row[j].x * scl, row[j].y * scl);
             }
         }
-        pix[j] = o; val[j] = v;
+        pix[j] = o; val[j] = v; col[j] = (int32_t)bx;
     }
     __syncthreads();
     for (int j = threadIdx.x; j < N; j += 256) {
         const int64_t o = pix[j];
         if (o < 0 || o == centre) continue;
+        const int32_t c = col[j];
         bool head = true;
-        for (int r = 1; r <= kRowRun && j - r >= 0; ++r) head = head && pix[j - r] != o;
+        for (int r = j - 1; r >= 0 && col[r] == c; --r)
+            if (pix[r] == o) { head = false; break; }
         if (!head) continue;
         double sr = val[j].x, si = val[j].y;
-        for (int r = 1; r <= kRowRun && j + r < N; ++r)
-            if (pix[j + r] == o) { sr = sr + val[j + r].x; si = si + val[j + r].y; }
+        for (int r = j + 1; r < N && col[r] == c; ++r)
+            if (pix[r] == o) { sr = sr + val[r].x; si = si + val[r].y; }
         const double scl = 1.0 / (double)cnt[o];                      // NumPy divides complex by real as v * (1 / c)
         auto clean = [](double x) { return x != x ? 0.0 : (x == INFINITY ? 1.7976931348623157e308 : (x == -INFINITY ? -1.7976931348623157e308 : x)); };
         recov[o] = mk(clean(sr * scl), clean(si * scl));
@@ -467,7 +475,8 @@ extern "C" int32_t scint_retrieval_tail_workspace_bytes(int64_t M, int64_t ntau,
     const int32_t rc = scint_fft2_workspace_bytes(ntau, nfd, &fft);
     if (rc != SCINT_OK) return rc;
     *bytes = align_up(sizeof(uint32_t) * (size_t)ntau * (size_t)nfd, 256) + align_up(sizeof(cplx) * (size_t)ntau * (size_t)nfd * kTailGroup, 256) +
-             align_up(fft, 256) + align_up((sizeof(int64_t) + sizeof(cplx)) * (size_t)M * kTailGroup, 256) + 512;
+             align_up(fft, 256) + align_up((sizeof(int64_t) + sizeof(cplx)) * (size_t)M * kTailGroup, 256) +
+             align_up(sizeof(int32_t) * (size_t)M * kTailGroup, 256) + 512;
     return SCINT_OK;
 }
 
@@ -490,6 +499,7 @@ extern "C" int32_t scint_retrieval_tail(const scint_c128* rows, const double* th
     char* fftws = (char*)recov + align_up(sizeof(cplx) * (size_t)npix * kTailGroup, 256);
     int64_t* pix = (int64_t*)(fftws + align_up(fft, 256));
     cplx* val = (cplx*)(pix + (size_t)M * kTailGroup);
+    int32_t* col = (int32_t*)((char*)pix + align_up((sizeof(int64_t) + sizeof(cplx)) * (size_t)M * kTailGroup, 256));
     int64_t k = 0;
     while (k < n) {
         int64_t e = k;
@@ -518,7 +528,7 @@ extern "C" int32_t scint_retrieval_tail(const scint_c128* rows, const double* th
                 if (cntm == 0) continue;
                 SCINT_HIP(hipMemsetAsync(recov, 0, sizeof(cplx) * (size_t)npix * (size_t)cntm, stream));
                 hipLaunchKernelGGL(rev_row_kernel, dim3((unsigned)cntm), dim3(256), 0, stream, (const cplx*)rows, th_red, M, members, (int)N, eta, g,
-                                   cnt, recov, centre, pix, val);
+                                   cnt, recov, centre, pix, val, col);
                 SCINT_LAUNCH_CHECK();
                 for (int q = 0; q < cntm; ++q) {
                     const int32_t rc = scint_ifft2_shifted((const scint_c128*)(recov + (size_t)q * (size_t)npix), ntau, nfd, scale, nf, nt,

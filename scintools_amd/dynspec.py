@@ -33,6 +33,13 @@ _WINDOWS = {"hanning": np.hanning, "hamming": np.hamming,
             "blackman": np.blackman, "bartlett": np.bartlett}
 
 
+def _walks_columns(a):
+    """True when ``np.copy(a[window])`` (order='K') lays the window out column by column, so that NumPy's sums over the copy
+    walk it that way: the first axis has the smaller stride.  Not only Fortran-contiguous arrays: a crop of a transposed array
+    is neither C- nor F-contiguous and is copied column-major too."""
+    return a.ndim == 2 and abs(a.strides[0]) < abs(a.strides[1])
+
+
 def get_window(nt, nf, window="hanning", frac=0.1):
     """Edge tapers with a flat middle (scint_utils.py:810-832); host NumPy,
     the multiply is fused into the first FFT pass on the device."""
@@ -591,8 +598,7 @@ class Dynspec:
                 origins.append((cf * (self.cwf // 2), ct * (self.cwt // 2)))
         dyn_h = np.asarray(self.dyn, dtype=float)
         dyn_t = thth.to_device(dyn_h, torch.float64)
-        d_t, pad_t = thth.chunk_cut_device(dyn_t, origins, self.cwf, self.cwt,
-                                           fortran_order=dyn_h.flags.f_contiguous and not dyn_h.flags.c_contiguous)
+        d_t, pad_t = thth.chunk_cut_device(dyn_t, origins, self.cwf, self.cwt, fortran_order=_walks_columns(dyn_h))
         out_t = thth.chunk_retrieval_batch(pars, self.npad, self.thth_tau_mask, verbose=verbose, dev_chunks=d_t,
                                            dev_pads=pad_t.cpu().numpy(), out_device=True)
         type(self).chunks.park(self, out_t.reshape(self.ncf_ret, self.nct_ret, self.cwf, self.cwt))

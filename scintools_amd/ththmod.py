@@ -1117,24 +1117,7 @@ def chunk_retrieval_batch(chunks, npad, tauMask, verbose=False, group_bytes=None
                 keep_n[j] = n
             except Exception as exc:
                 print("Chunk %d: %s" % (g0 + k, exc), flush=True)
-        rows_t, th_all_t = _dv.to_device(rows_all, torch.complex128), _dv.to_device(th_all, torch.float64)
-        out_t = torch.zeros((len(live), nf, nt), dtype=torch.complex128, device=dev)
-        geoms = (_lib.CsGeom * len(live))(*[g_.geom for g_ in grids])
-        etas_a = np.ascontiguousarray([float(e_[0]) for e_ in etas], dtype=np.float64)
-        # classes: consecutive chunks with the same reduced centres, curvature and axes (the chunks of one frequency row) share the
-        # pair counts of their back-maps
-        class_id, prev, cid = np.zeros(len(live), dtype=np.int32), None, -1
-        for j in range(len(live)):
-            key = (float(etas_a[j]), int(keep_n[j]), th_all[j, :keep_n[j]].tobytes(), bytes(grids[j].geom))
-            if key != prev:
-                cid, prev = cid + 1, key
-            class_id[j] = cid
-        _lib.check(lib.scint_retrieval_tail_workspace_bytes(M, R, C, ctypes.byref(need)), "retrieval_tail_workspace_bytes")
-        ws = workspace.get(need.value)
-        _lib.check(lib.scint_retrieval_tail(ptr(rows_t), ptr(th_all_t), keep_n.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                            class_id.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), geoms,
-                                            etas_a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(live), M, nf, nt, nf * nt / 4,
-                                            ptr(out_t), ptr(ws), ws.numel(), stream_ptr()), "scint_retrieval_tail")
+        out_t = _retrieval_tail_dev(rows_all, th_all, keep_n, None, grids, [float(e_[0]) for e_ in etas], nf, nt)
         if verbose:
             for j, k in enumerate(live):
                 if keep_n[j] >= 2:
@@ -1145,8 +1128,46 @@ def chunk_retrieval_batch(chunks, npad, tauMask, verbose=False, group_bytes=None
             out[g0 + np.asarray(live)] = out_t.cpu().numpy()
         # release this group's device buffers BEFORE the next group allocates its own: while the names are bound the caching
         # allocator cannot reuse the blocks and the peak would be two groups -- the bound is `group_bytes`, not twice it
-        del stack, V_t, out_t, d_t, rows_t, th_all_t, ws
+        del stack, V_t, out_t, d_t, ws
     return out
+
+
+def _retrieval_tail_dev(rows, th_red, keep_n, class_id, grids, etas, nf, nt, out_t=None):
+    """The tail of :func:`chunk_retrieval_batch` (scint_retrieval_tail): per chunk k with keep_n[k] >= 2, the theta-theta matrix
+    of the E field that is zero but for row N/2 = rows[k, :N], its non-Hermitian back-map on the reduced centres th_red[k, :N]
+    (ththmod.py:1457-1464) and nf nt / 4 * ifft2(ifftshift(.))[:nf, :nt].  rows: host complex [n, M]; th_red: host float [n, M];
+    keep_n: int [n]; grids / etas: the chunk's _Grid and curvature.  class_id: int [n], consecutive chunks with equal ids share
+    the pair counts of their back-maps (the caller's promise); None = the classes of equal (curvature, centres, axes).
+    ``out_t``: device [n, nf, nt] complex128 the result is written into (chunks with keep_n < 2 keep what it holds); default
+    zeros.  Returns the device tensor."""
+    lib = _lib.load()
+    n, M = (int(v) for v in np.shape(rows))
+    keep_n = np.ascontiguousarray(keep_n, dtype=np.int32)
+    etas_a = np.ascontiguousarray(etas, dtype=np.float64)
+    th_red = np.asarray(th_red, dtype=float)
+    if class_id is None:
+        # classes: consecutive chunks with the same reduced centres, curvature and axes (the chunks of one frequency row) share the
+        # pair counts of their back-maps
+        class_id, prev, cid = np.zeros(n, dtype=np.int32), None, -1
+        for j in range(n):
+            key = (float(etas_a[j]), int(keep_n[j]), th_red[j, :keep_n[j]].tobytes(), bytes(grids[j].geom))
+            if key != prev:
+                cid, prev = cid + 1, key
+            class_id[j] = cid
+    class_id = np.ascontiguousarray(class_id, dtype=np.int32)
+    rows_t, th_t = _dv.to_device(np.asarray(rows, dtype=complex), torch.complex128), _dv.to_device(th_red, torch.float64)
+    if out_t is None:
+        out_t = torch.zeros((n, nf, nt), dtype=torch.complex128, device=require_gpu())
+    geoms = (_lib.CsGeom * n)(*[g_.geom for g_ in grids])
+    need = ctypes.c_size_t()
+    _lib.check(lib.scint_retrieval_tail_workspace_bytes(M, grids[0].geom.ntau, grids[0].geom.nfd, ctypes.byref(need)),
+               "retrieval_tail_workspace_bytes")
+    ws = workspace.get(need.value)
+    _lib.check(lib.scint_retrieval_tail(ptr(rows_t), ptr(th_t), keep_n.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                        class_id.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), geoms,
+                                        etas_a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n, M, nf, nt, nf * nt / 4,
+                                        ptr(out_t), ptr(ws), ws.numel(), stream_ptr()), "scint_retrieval_tail")
+    return out_t
 
 
 def single_chunk_retrieval(params):
@@ -1256,9 +1277,14 @@ def _numpy_mosaic_modes(cwf, cwt):
 def _mosaic_tapers(ncf, nct, cwf, cwt):
     """The taper of chunk (cf, ct) as mask[r, c] = fr[r] * fc[c] (ththmod.py:1526-1546 builds it by multiplying a matrix of ones
     by a row factor, then by a column factor: one product per element, the same bits).  Returns (rows[4, cwf], cols[4, cwt]) and
-    the index function: variant 2 * (has a neighbour before) + (has a neighbour after)."""
-    def variants(w):
+    the index function: variant 2 * (has a neighbour before) + (has a neighbour after).  An axis of ONE chunk uses variant 0 only
+    (no taper): its size may be odd, and the other variants stay ones."""
+    def variants(w, nchunk):
         v = np.ones((4, w))
+        if nchunk == 1:
+            return v
+        if w % 2:
+            raise ValueError("mosaic: chunk sizes must be even along an axis of several chunks (the reference's half-overlap tapers)")
         mf = mask_func(w // 2)
         for k in range(4):
             if k & 2:
@@ -1266,7 +1292,7 @@ def _mosaic_tapers(ncf, nct, cwf, cwt):
             if k & 1:
                 v[k, w // 2:] *= 1 - mf
         return v
-    return variants(cwf), variants(cwt)
+    return variants(cwf, ncf), variants(cwt, nct)
 
 
 def mosaic_device(chunks_t):
@@ -1280,10 +1306,8 @@ def mosaic_device(chunks_t):
     chunks (tests); the host loop spent 0.26 s on those 961 chunks and needed them on the host (1 GB)."""
     lib = _lib.load()
     ncf, nct, cwf, cwt = (int(v) for v in chunks_t.shape)
-    if cwf % 2 or cwt % 2:
-        raise ValueError("mosaic: chunk sizes must be even (the reference's half-overlap tapers)")
+    rows, cols = _mosaic_tapers(ncf, nct, cwf, cwt)             # (raises for an odd size along an axis of several chunks)
     F, T = (ncf - 1) * (cwf // 2) + cwf, (nct - 1) * (cwt // 2) + cwt
-    rows, cols = _mosaic_tapers(ncf, nct, cwf, cwt)
     rows_t, cols_t = _dv.to_device(rows, torch.float64), _dv.to_device(cols, torch.float64)
     E_t = torch.zeros((F, T), dtype=torch.complex128, device=chunks_t.device)
     modes = _numpy_mosaic_modes(cwf, cwt)

@@ -611,22 +611,28 @@ def test_device_mosaic_is_the_host_loop_bit_for_bit(emu, shape):
     assert np.array_equal(got, emu.mosaic(ch))
 
 
-@pytest.mark.parametrize("fortran", [False, True])
+@pytest.mark.parametrize("fortran", [False, True, "crop of a transposed array"])
 @pytest.mark.parametrize("cw", [(64, 150), (128, 128), (16, 12), (20, 30)])
 def test_device_chunk_cut_is_numpy_bit_for_bit(emu, cw, fortran):
     """ththmod.chunk_cut_device against the reference's three lines per chunk (dynspec.py:1782-1790: copy, subtract nanmean,
     nan_to_num) and the padding value (the chunk's mean, ththmod.py:783), NaNs in some windows: the same bits -- also for a
-    Fortran-ordered dynamic spectrum (a transposed view, as files load), whose windows NumPy copies and sums column by column."""
+    Fortran-ordered dynamic spectrum (a transposed view, as files load), whose windows NumPy copies and sums column by column,
+    and for a crop of one (neither C- nor F-contiguous: Dynspec.thetatheta_chunks takes the order from the strides)."""
     import torch
+    from scintools_amd.dynspec import _walks_columns
     rng = np.random.default_rng(5)
     dyn = rng.standard_normal((200, 300)) * 5 + 3
     dyn[5, 7] = np.nan
     dyn[100:120, 40] = np.nan
-    if fortran:
+    if fortran is True:
         dyn = np.asfortranarray(dyn)
+    elif fortran:
+        dyn = np.asfortranarray(np.pad(dyn, ((3, 2), (4, 1))))[3:-2, 4:-1]
+        assert not dyn.flags.c_contiguous and not dyn.flags.f_contiguous
+    assert _walks_columns(dyn) == bool(fortran)
     cwf, cwt = cw
     org = [(0, 0), (10, 20), (200 - cwf, 300 - cwt), (min(90, 200 - cwf), 30)]
-    out, pad = emu.chunk_cut_device(torch.from_numpy(np.ascontiguousarray(dyn)), org, cwf, cwt, fortran_order=fortran)
+    out, pad = emu.chunk_cut_device(torch.from_numpy(np.ascontiguousarray(dyn)), org, cwf, cwt, fortran_order=_walks_columns(dyn))
     for k, (r, c) in enumerate(org):
         d2 = np.copy(dyn[r:r + cwf, c:c + cwt])
         d2 -= np.nanmean(d2)

@@ -455,22 +455,35 @@ def test_phase_retrieval_vs_reference_golden(thth, golden):
 
 
 def test_retrieval_tail_on_the_device_equals_the_host_fed_path_bit_for_bit(thth, golden):
+    _device_cut_and_mosaic_vs_host_fed(thth, golden, cropped=False)
+
+
+def test_device_chunk_cut_of_a_cropped_transposed_dyn_equals_the_host_fed_path_bit_for_bit(thth, golden):
+    _device_cut_and_mosaic_vs_host_fed(thth, golden, cropped=True)
+
+
+def _device_cut_and_mosaic_vs_host_fed(thth, golden, cropped):
     """Round 6: Dynspec.thetatheta_chunks cuts its chunks on the device (ththmod.chunk_cut_device: window, nanmean, nan_to_num and
     the padding value in NumPy's summation order) and calc_wavefield mosaics them there (ththmod.mosaic_device).  Against the
     host-fed forms on the same data -- chunk_retrieval_batch with the reference's three lines per chunk on the host
     (dynspec.py:1782-1790), and the host loop ththmod.mosaic (ththmod.py:1492-1554) -- not a bit differs; a dynamic spectrum with
-    NaNs included."""
-    from scintools_amd.dynspec import Dynspec
+    NaNs included.  The golden `dspec` is Fortran-ordered (as files load); `cropped`: a crop of such an array (neither C- nor
+    F-contiguous), whose windows NumPy still copies and sums column by column."""
+    from scintools_amd.dynspec import Dynspec, _walks_columns
     f = golden("fit_thetatheta.npz")
     n = 256
     dyn = np.array(f["dspec"][:n], dtype=float)
     dyn[17, 40:44] = np.nan
+    if cropped:
+        dyn = np.asfortranarray(np.pad(dyn, ((2, 3), (1, 4))))[2:-3, 1:-4]
 
     class B:
         pass
     B.dyn, B.freqs, B.times, B.dt, B.df = dyn, f["freq"][:n], f["time"], float(f["dt"]), float(f["df"])
     d = Dynspec(dyn=B(), verbose=False)
     d.prep_thetatheta(cwf=64, edges_lim=.3, eta_min=30, eta_max=50, nedge=128)
+    if cropped:
+        assert _walks_columns(d.dyn) and not d.dyn.flags.c_contiguous and not d.dyn.flags.f_contiguous
     d.calc_wavefield()
     chunks_dev, wf_dev = d.chunks.copy(), d.wavefield.copy()
     pars = []
