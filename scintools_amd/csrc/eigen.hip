@@ -44,7 +44,7 @@ struct LanczosJob {
     cplx* W[2];         // ping-pong work vectors [n]
     cplx* Q;            // q vectors: [qslots][n]
     int32_t qslots;     // 2 (ring) or max_steps (kept for the eigenvector)
-    int32_t pad0;
+    int32_t rank;       // an upper bound of rank(A) if one is known (the Krylov space is exhausted after rank + 1 steps), or 0
     double* alpha;      // [max_steps]
     double* beta;       // [max_steps + 1]; beta[0] = |v0|, beta[j] = |w| after step j-1
     double* apart;      // [ceil(n/32)]   partial q_j^H u per matvec block
@@ -237,6 +237,11 @@ __global__ void __launch_bounds__(64) lanczos_check_kernel(const LanczosJob* job
         scale = fmax(scale, __shfl_xor(scale, o, 64));
     }
     bool finite = isfinite(lo) && isfinite(hi) && isfinite(beta_k);
+    // A job that knows rank(A) <= r (B = A^H A of a map with r rows) has exhausted its Krylov space after r + 1 steps: T_k
+    // then holds lambda_1 exactly.  Past that point the recurrence restarts from rounding noise and grows a second copy of
+    // lambda_1; until that copy has converged too, the top pair of T_k is a near-degenerate mix whose last component is not
+    // small, and the residual rule alone would let the job wander for tens of steps.
+    const bool exhausted = jb.rank > 0 && k > jb.rank;
     double theta = nan(""), resid = nan("");
     if (finite) {
         const double tiny = fmax(scale, 1e-300) * 1e-300 + 1e-300;
@@ -289,7 +294,7 @@ __global__ void __launch_bounds__(64) lanczos_check_kernel(const LanczosJob* job
         resid = __shfl(resid, 0, 64);
     }
     if (lane == 0) {
-        const bool conv = finite && (resid <= jb.tol * fmax(fabs(theta), 1e-300) || k >= n || beta_k == 0.0);
+        const bool conv = finite && (resid <= jb.tol * fmax(fabs(theta), 1e-300) || k >= n || beta_k == 0.0 || exhausted);
         const bool stop = conv || !finite || k >= jb.max_steps || final_pass;
         jb.result[0] = theta;
         jb.result[1] = resid;
@@ -437,7 +442,7 @@ extern "C" int32_t scint_eigh_top(const scint_c128* a, int64_t n, const scint_c1
     LanczosJob jb;
     jb.A = (const cplx*)a; jb.ld = n; jb.n = (int32_t)n; jb.max_steps = steps;
     jb.W[0] = (cplx*)(base + L.W0); jb.W[1] = (cplx*)(base + L.W1);
-    jb.Q = (cplx*)(base + L.Q); jb.qslots = steps; jb.pad0 = 0;
+    jb.Q = (cplx*)(base + L.Q); jb.qslots = steps; jb.rank = 0;
     jb.alpha = (double*)(base + L.alpha); jb.beta = (double*)(base + L.beta);
     jb.apart = (double*)(base + L.apart); jb.npart = (double*)(base + L.npart);
     jb.svec = (double*)(base + L.svec); jb.result = (double*)(base + L.result);
@@ -852,7 +857,7 @@ extern "C" int32_t scint_sv_sweep_multi(const scint_c128* cs_stack, int64_t ncs,
             if (b.n1 >= 2 && b.n2 >= 1) { cls_used[b.cls] = true; nmax_steps = std::max(nmax_steps, b.max_steps); }
             LanczosJob& l = lj[j];
             l = LanczosJob{};
-            l.n = b.n1; l.max_steps = b.max_steps; l.qslots = 2;
+            l.n = b.n1; l.max_steps = b.max_steps; l.qslots = 2; l.rank = b.n2;
             l.alpha = b.alpha; l.beta = b.beta; l.apart = b.apart; l.npart = b.npart;
             l.svec = nullptr; l.result = (double*)(s + L.result);
             l.state = b.state; l.eig_out = b.lam; l.status_out = b.status; l.iters_out = b.iters;

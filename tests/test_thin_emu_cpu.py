@@ -10,6 +10,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "emu"))
 sys.path.insert(0, HERE)
+import thin_cases as tc  # noqa: E402
 import thin_oracle as to  # noqa: E402
 
 
@@ -125,6 +126,74 @@ def test_multi_chunk_call_equals_chunk_by_chunk(emu, small):
     one_by_one = emu.sv_sweep_multi(stack, grids, etas, 0.02, batch=1)
     for k in range(2):
         assert np.array_equal(one_by_one[k], both[k])
+
+
+# ---- the small members of the MI355X case list (tests/thin_cases.py, tests/test_gpu_thin_classes.py) --------------------------
+@pytest.fixture(scope="module")
+def ax():
+    return tc.axes()
+
+
+@pytest.fixture(scope="module")
+def spectra():
+    return {k: tc.spectrum(k) for k in ("arc", "gauss", "zero")}
+
+
+@pytest.mark.parametrize("n1,n2,kind,cutf", tc.small_class_cases() + [(150, 300, "arc", 0.02), (257, tc.N2_TALL, "gauss", 0.02), (4097, 3, "arc", 0.0),
+                                                                  (8193, 2, "gauss", 0.0)],
+                         ids=lambda v: str(v))
+def test_class_cases_against_lapack(emu, ax, spectra, n1, n2, kind, cutf):
+    """Classes 0, 1 and 2 (n1 <= 513) with 1, 2, 3, 4, 5 and 11 rows, one R = 4 map of 75 strips, one tall map (R = 6, last strip
+    of 5 rows) and one few-row map in each of the 512- and 1024-thread classes: the assertions of
+    test_gpu_thin_classes.py::test_class_against_lapack."""
+    tau, fd = ax
+    g = tc.grid(n1, n2, tau, fd)
+    eta = tc.eta0(tau, fd)
+    cut = cutf * fd.max()
+    ref = tc.oracle_sv(spectra[kind], tau, fd, eta, g[2], eta, g[3], cut)
+    sv, info = emu.sv_sweep_multi(spectra[kind][None], [g], [np.array([eta])], cut, return_info=True)
+    assert int(info["ranges"][0, 3]) == n1 and int(info["ranges"][0, 1]) == n2
+    assert info["status"][0] == 0
+    assert sv[0][0] == pytest.approx(ref, rel=1e-10, abs=0)
+    assert info["iters"][0] < tc.MAX_ITER
+    if n2 < tc.FIRST_CHECK:
+        assert info["iters"][0] <= tc.FIRST_CHECK
+
+
+@pytest.mark.parametrize("n1,n2", [(200, 9), (513, 6)])
+def test_zero_middle_row(emu, ax, spectra, n1, n2):
+    tau, fd = ax
+    g = tc.grid(n1, n2, tau, fd)
+    eta = tc.eta0(tau, fd)
+    CS = tc.zero_middle_row(spectra["gauss"], tau, fd, eta, g[2], g[3])
+    ref = tc.oracle_sv(CS, tau, fd, eta, g[2], eta, g[3], 0.0)
+    sv, info = emu.sv_sweep_multi(CS[None], [g], [np.array([eta])], 0.0, return_info=True)
+    assert info["status"][0] == 0 and ref > 0
+    assert sv[0][0] == pytest.approx(ref, rel=1e-10, abs=0)
+    assert info["iters"][0] <= tc.FIRST_CHECK
+
+
+@pytest.mark.parametrize("value", [np.nan, np.inf])
+def test_non_finite_pixel(emu, ax, spectra, value):
+    from scintools_amd import _lib
+    tau, fd = ax
+    g = tc.grid(300, 9, tau, fd)
+    eta = tc.eta0(tau, fd)
+    clean = spectra["arc"]
+    bad = tc.poisoned(clean, tau, fd, eta, g[2], g[3], value, which=3)
+    sv, info = emu.sv_sweep_multi(np.stack([bad, clean]), [g, g], [np.array([eta])] * 2, 0.0, return_info=True)
+    assert np.isnan(sv[0][0]) and info["status"][0] == _lib.SCINT_E_NONFINITE
+    assert sv[1][0] == pytest.approx(tc.oracle_sv(clean, tau, fd, eta, g[2], eta, g[3], 0.0), rel=1e-10, abs=0)
+    with pytest.raises(np.linalg.LinAlgError):
+        emu.singularvalue_calc(bad, tau, fd, eta, g[2], eta, g[3], 0.0)
+
+
+def test_column_limit_names_the_limit(emu, ax, spectra):
+    from scintools_amd._lib import ScintHipError
+    tau, fd = ax
+    g = tc.grid(tc.SV_MAX_COLS + 1, 2, tau, fd)
+    with pytest.raises(ScintHipError, match="16384"):
+        emu.sv_sweep_multi(spectra["arc"][None], [g], [np.array([4.0 * tc.eta0(tau, fd)])])
 
 
 PROBE = os.path.join(HERE, "thin_order_probe.py")
