@@ -265,6 +265,18 @@ int32_t scint_eigh_top(const scint_c128* a, int64_t n, const scint_c128* v0,
                        int32_t* status_out, int32_t* iters_out,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same for MANY dense Hermitian matrices in one set of launches: job j is the n[j] x n[j] row-major matrix at
+ * a_stack + j * a_stride, started from its row start_row[j] (HOST [njobs]; NULL = the middle row n[j] / 2).  w_out[njobs],
+ * vec_out[njobs][vec_stride] (row j holds n[j] entries, the rest is left as it was), status_out[njobs], iters_out[njobs]: device.
+ * n, start_row: HOST.  A job with n[j] < 2 gets SCINT_E_EMPTY.  A job's arithmetic does not depend on which jobs share the call.
+ * Synchronous (the done flags are read back every few steps, as in scint_eigh_top).  njobs <= 65535. */
+int32_t scint_eigh_top_batch_workspace_bytes(int64_t nmax, int32_t max_iter, int64_t njobs, size_t* bytes /*HOST*/);
+int32_t scint_eigh_top_batch(const scint_c128* a_stack, int64_t a_stride, const int32_t* n /*HOST*/,
+                             const int32_t* start_row /*HOST or NULL*/, int64_t njobs, double tol, int32_t max_iter,
+                             double* w_out, scint_c128* vec_out, int64_t vec_stride,
+                             int32_t* status_out, int32_t* iters_out,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- theta-theta -> CS: rev_map (ththmod.py:176-271) --------------------- */
 /* thth[N,N] on centres th_cents[N] (already re-centred) -> recov[ntau,nfd].
  * If `rank1` != 0, thth is not read: thth = |w| V V^H with V = vec[N], w = *w
@@ -350,6 +362,32 @@ int32_t scint_retrieval_tail_workspace_bytes(int64_t M, int64_t ntau, int64_t nf
 int32_t scint_retrieval_tail(const scint_c128* rows, const double* th_red, const int32_t* keep_n /*HOST*/, const int32_t* class_id /*HOST*/,
                              const scint_cs_geom* geoms /*HOST*/, const double* etas /*HOST*/, int64_t n, int64_t M, int64_t nf, int64_t nt,
                              double scale, scint_c128* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- multi-station (VLBI) phase retrieval: VLBI_chunk_retrieval (ththmod.py:1223-1387), a group of chunks per call
+ * A chunk of n_dish stations has nspec = n_dish (n_dish + 1) / 2 spectra in the reference's order [I1, V12, .., V1N, I2, V23, .., IN]:
+ * the dynamic spectra go through scint_cs_batch (mean-padded, real), the visibilities through
+ * scint_cs_complex_batch: cs_stack[k] = fftshift(fft2(np.pad(xstack[k], right/bottom by npad * shape, 0))) of COMPLEX
+ *   xstack [n][nf][nt], rows mask_lohi[k][0] <= r < mask_lohi[k][1] (HOST [n][2]) written as zero (ththmod.py:1313-1325).
+ *   Workspace: scint_cs_workspace_bytes().
+ * scint_vlbi_composite: the composite theta-theta of every chunk (ththmod.py:1292-1362).  Spectrum idx of chunk k is the
+ *   conjugate spectrum at cs_stack + cs_slot[k * nspec + idx] * cs_stride (cs_slot: HOST) on geoms[k] (HOST); the chunk keeps the
+ *   keep_n[k] (HOST) centres keep_idx[k * M ..] of th_stack[k * M ..] (the crop of thth_redmap: one per chunk) at curvature etas[k]
+ *   (HOST).  With N = keep_n[k], the composite is the dense row-major [n_dish N][n_dish N] matrix at comp_out + k * comp_stride:
+ *   for station pair (d1, d1 + d2) the reduced theta-theta T of spectrum idx(d1, d2) (ththmod.py:1345-1349) is block
+ *   (d1 + d2, d1) and conj(T^T) block (d1, d1 + d2); T is thth_redmap with hermetian=True when d2 == 0 (ththmod.py:108-114) and
+ *   hermetian=False otherwise (no forcing, no nan_to_num, nothing zeroed).  Every element of the composite is written; a CS pixel
+ *   is read once for both blocks.  An element whose Doppler index lies below -nfd (NumPy raises IndexError) is NaN.
+ *   Workspace: scint_vlbi_composite_workspace_bytes().  Synchronous.
+ * The dominant eigenpair of the composites: scint_eigh_top_batch; the wavefields: scint_retrieval_tail with n_dish rows per chunk. */
+int32_t scint_cs_complex_batch(const scint_c128* xstack, int64_t n, int64_t nf, int64_t nt, int64_t npad,
+                               const int64_t* mask_lohi /*HOST*/, scint_c128* cs_stack, void* workspace,
+                               size_t workspace_bytes, void* stream);
+int32_t scint_vlbi_composite_workspace_bytes(int64_t nchunk, int64_t n_dish, size_t* bytes /*HOST*/);
+int32_t scint_vlbi_composite(const scint_c128* cs_stack, int64_t cs_stride, const int64_t* cs_slot /*HOST*/,
+                             const scint_cs_geom* geoms /*HOST*/, const double* th_stack, int64_t M,
+                             const int32_t* keep_idx, const int32_t* keep_n /*HOST*/, const double* etas /*HOST*/,
+                             int64_t nchunk, int64_t n_dish, scint_c128* comp_out, int64_t comp_stride,
+                             void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Gerchberg-Saxton iterations of Dynspec.gerchberg_saxton (dynspec.py:1868-1875) -------
  * wavefield[rows, cols] in place.  Per iteration: fft2, zero the natural-order delay rows

@@ -94,6 +94,13 @@ _SIGNATURES = {
     "scint_mosaic_add": ([_P, c_int64, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int32, POINTER(c_double), _P], c_int32),
     "scint_chunk_cut": ([_P, c_int64, c_int64, _P, _P, c_int64, c_int64, c_int64, c_int32, _P, _P, _P, c_size_t, _P], c_int32),
     "scint_cs_batch": ([_P, c_int64, c_int64, c_int64, c_int64, POINTER(c_double), POINTER(c_int64), c_int32, _P, _P, c_size_t, _P], c_int32),
+    "scint_cs_complex_batch": ([_P, c_int64, c_int64, c_int64, c_int64, POINTER(c_int64), _P, _P, c_size_t, _P], c_int32),
+    "scint_vlbi_composite_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
+    "scint_vlbi_composite": ([_P, c_int64, POINTER(c_int64), POINTER(CsGeom), _P, c_int64, _P, POINTER(c_int32), POINTER(c_double),
+                              c_int64, c_int64, _P, c_int64, _P, c_size_t, _P], c_int32),
+    "scint_eigh_top_batch_workspace_bytes": ([c_int64, c_int32, c_int64, POINTER(c_size_t)], c_int32),
+    "scint_eigh_top_batch": ([_P, c_int64, POINTER(c_int32), POINTER(c_int32), c_int64, c_double, c_int32, _P, _P, c_int64, _P, _P,
+                              _P, c_size_t, _P], c_int32),
     "scint_retrieval_tail_workspace_bytes": ([c_int64, c_int64, c_int64, POINTER(c_size_t)], c_int32),
     "scint_retrieval_tail": ([_P, _P, POINTER(c_int32), POINTER(c_int32), POINTER(CsGeom), POINTER(c_double), c_int64, c_int64, c_int64, c_int64,
                               c_double, _P, _P, c_size_t, _P], c_int32),
@@ -148,6 +155,12 @@ def load():
     # runtimes and ours then sees no device).
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
+    # An entry point may be ADDED without a new ABI version (the version guards the argument lists of the existing ones): a stale
+    # build that lacks one must say so here, not fail with an AttributeError in the middle of a call.
+    missing = [name for name in _SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise ScintHipError(f"{LIB_PATH} lacks {', '.join(missing)}: it was built from older sources; "
+                            "rebuild it with `python -m scintools_amd.build`")
     for name, (argtypes, restype) in _SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes

@@ -311,9 +311,11 @@ __global__ void __launch_bounds__(64) lanczos_check_kernel(const LanczosJob* job
 }
 
 // Ritz vector y = sum_j s_j q_j (un-normalised) + partial |y|^2
-__global__ void __launch_bounds__(kVecBlock) lanczos_ritz_kernel(const LanczosJob* jobs, cplx* out) {
+// (out_stride: elements between the vectors of consecutive jobs, scint_eigh_top_batch)
+__global__ void __launch_bounds__(kVecBlock) lanczos_ritz_kernel(const LanczosJob* jobs, cplx* out, int64_t out_stride) {
     __shared__ double red[kVecBlock / 64];
     const LanczosJob jb = jobs[blockIdx.y];
+    out += (int64_t)blockIdx.y * out_stride;
     const int n = jb.n, k = jb.state[1];
     if (blockIdx.x * kVecBlock >= n) return;
     const int r = blockIdx.x * kVecBlock + threadIdx.x;
@@ -332,16 +334,17 @@ __global__ void __launch_bounds__(kVecBlock) lanczos_ritz_kernel(const LanczosJo
     if (threadIdx.x == 0) jb.npart[blockIdx.x] = p;
 }
 
-__global__ void __launch_bounds__(kVecBlock) lanczos_scale_kernel(const LanczosJob* jobs, cplx* out,
+__global__ void __launch_bounds__(kVecBlock) lanczos_scale_kernel(const LanczosJob* jobs, cplx* out, int64_t out_stride,
                                                                   double* w_out) {
     const LanczosJob jb = jobs[blockIdx.y];
+    out += (int64_t)blockIdx.y * out_stride;
     const int n = jb.n;
     const int r = blockIdx.x * kVecBlock + threadIdx.x;
     const int nvb = (n + kVecBlock - 1) / kVecBlock;
     const double nrm = sqrt(sum_partials(jb.npart, nvb));
     const double inv = nrm > 0.0 ? 1.0 / nrm : 0.0;
     if (r < n) out[r] = mk(out[r].x * inv, out[r].y * inv);
-    if (r == 0 && w_out) w_out[0] = jb.result[0];
+    if (r == 0 && w_out) w_out[blockIdx.y] = jb.result[0];
 }
 
 // ------------------------------------------------------------------------------
@@ -458,12 +461,79 @@ extern "C" int32_t scint_eigh_top(const scint_c128* a, int64_t n, const scint_c1
     if (rc != SCINT_OK) return rc;
     if (vec_out) {
         const dim3 vgrid((unsigned)ceil_div(n, kVecBlock), 1);
-        hipLaunchKernelGGL(lanczos_ritz_kernel, vgrid, dim3(kVecBlock), 0, stream, jd, (cplx*)vec_out);
-        hipLaunchKernelGGL(lanczos_scale_kernel, vgrid, dim3(kVecBlock), 0, stream, jd, (cplx*)vec_out, w_out);
+        hipLaunchKernelGGL(lanczos_ritz_kernel, vgrid, dim3(kVecBlock), 0, stream, jd, (cplx*)vec_out, (int64_t)0);
+        hipLaunchKernelGGL(lanczos_scale_kernel, vgrid, dim3(kVecBlock), 0, stream, jd, (cplx*)vec_out, (int64_t)0, w_out);
         SCINT_LAUNCH_CHECK();
     } else {
         SCINT_HIP(hipMemcpyAsync(w_out, jb.result, sizeof(double), hipMemcpyDeviceToDevice, stream));
     }
+    SCINT_HIP(hipStreamSynchronize(stream));
+    return SCINT_OK;
+}
+
+
+// ------------------------------------------------------------------------------
+// scint_eigh_top_batch: scint_eigh_top of MANY dense Hermitian matrices in one set of launches (the composite theta-theta
+// matrices of a group of VLBI chunks, ththmod.py:1365).  The Lanczos kernels above are batched over jobs in blockIdx.y; job j
+// is the n[j] x n[j] matrix at a_stack + j * a_stride (row length n[j]), started from its row start_row[j] (its middle row when
+// start_row is null).  A job's arithmetic does
+// not depend on which jobs share the call.  n[j] < 2: status SCINT_E_EMPTY, the vector left as it was.
+// ------------------------------------------------------------------------------
+extern "C" int32_t scint_eigh_top_batch_workspace_bytes(int64_t nmax, int32_t max_iter, int64_t njobs, size_t* bytes) {
+    SCINT_REQUIRE(bytes && nmax >= 1 && max_iter >= 1 && njobs >= 1, "eigh_top_batch_workspace_bytes: bad arguments");
+    const int steps = (int)std::min<int64_t>(max_iter, nmax);
+    JobLayout L = job_layout(nmax, steps, steps, false, nullptr);
+    *bytes = L.total * (size_t)njobs + align_up(sizeof(LanczosJob) * (size_t)njobs, 256) + align_up(sizeof(int32_t) * 4 * (size_t)njobs, 256) + 1024;
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_eigh_top_batch(const scint_c128* a_stack, int64_t a_stride, const int32_t* n, const int32_t* start_row,
+                                        int64_t njobs, double tol, int32_t max_iter, double* w_out, scint_c128* vec_out, int64_t vec_stride,
+                                        int32_t* status_out, int32_t* iters_out, void* workspace, size_t workspace_bytes,
+                                        void* stream_) {
+    SCINT_REQUIRE(a_stack && n && w_out && vec_out && status_out && iters_out && workspace, "eigh_top_batch: null pointer");
+    SCINT_REQUIRE(njobs >= 1 && njobs <= 65535 && max_iter >= 1 && tol > 0, "eigh_top_batch: bad arguments");
+    hipStream_t stream = (hipStream_t)stream_;
+    int64_t nmax = 1;
+    for (int64_t j = 0; j < njobs; ++j) {
+        SCINT_REQUIRE(n[j] >= 0 && (int64_t)n[j] * n[j] <= a_stride && n[j] <= vec_stride, "eigh_top_batch: matrix larger than its slot");
+        SCINT_REQUIRE(!start_row || n[j] == 0 || (start_row[j] >= 0 && start_row[j] < n[j]), "eigh_top_batch: start row outside the matrix");
+        nmax = std::max<int64_t>(nmax, n[j]);
+    }
+    size_t need = 0;
+    scint_eigh_top_batch_workspace_bytes(nmax, max_iter, njobs, &need);
+    if (workspace_bytes < need) { set_error("scint: eigh_top_batch workspace too small"); return SCINT_E_WORKSPACE; }
+    const int steps_max = (int)std::min<int64_t>(max_iter, nmax);
+    const JobLayout L = job_layout(nmax, steps_max, steps_max, false, nullptr);
+    std::vector<LanczosJob> jobs((size_t)njobs);
+    LanczosJob* jd = (LanczosJob*)((char*)workspace + L.total * (size_t)njobs);
+    // the done flags of all jobs in ONE array (run_lanczos reads 4 words per job back with one copy), not in the jobs' slabs
+    int32_t* states = (int32_t*)((char*)jd + align_up(sizeof(LanczosJob) * (size_t)njobs, 256));
+    for (int64_t j = 0; j < njobs; ++j) {
+        char* base = (char*)workspace + L.total * (size_t)j;
+        LanczosJob& jb = jobs[(size_t)j];
+        const int steps = (int)std::min<int64_t>(max_iter, std::max<int64_t>(n[j], 1));
+        jb.A = (const cplx*)a_stack + j * a_stride; jb.ld = n[j]; jb.n = n[j]; jb.max_steps = steps;
+        jb.W[0] = (cplx*)(base + L.W0); jb.W[1] = (cplx*)(base + L.W1);
+        jb.Q = (cplx*)(base + L.Q); jb.qslots = steps; jb.rank = 0;
+        jb.alpha = (double*)(base + L.alpha); jb.beta = (double*)(base + L.beta);
+        jb.apart = (double*)(base + L.apart); jb.npart = (double*)(base + L.npart);
+        jb.svec = (double*)(base + L.svec); jb.result = (double*)(base + L.result);
+        jb.state = states + 4 * j;
+        jb.eig_out = nullptr; jb.status_out = status_out + j; jb.iters_out = iters_out + j;
+        jb.v0 = (start_row && n[j] > 0) ? jb.A + (int64_t)start_row[j] * n[j] : nullptr; jb.tol = tol;
+    }
+    SCINT_HIP(hipMemcpyAsync(jd, jobs.data(), sizeof(LanczosJob) * jobs.size(), hipMemcpyHostToDevice, stream));
+    int32_t* flags = nullptr;
+    SCINT_HIP(hipHostMalloc(&flags, sizeof(int32_t) * 4 * (size_t)njobs));
+    const int32_t rc = run_lanczos(jd, states, (int)njobs, (int)nmax, max_iter, flags, stream);
+    if (rc != SCINT_OK) (void)hipStreamSynchronize(stream);     // `jobs` (the source of the copy above) and `flags` go away here
+    (void)hipHostFree(flags);
+    if (rc != SCINT_OK) return rc;
+    const dim3 vgrid((unsigned)ceil_div(nmax, kVecBlock), (unsigned)njobs);
+    hipLaunchKernelGGL(lanczos_ritz_kernel, vgrid, dim3(kVecBlock), 0, stream, jd, (cplx*)vec_out, vec_stride);
+    hipLaunchKernelGGL(lanczos_scale_kernel, vgrid, dim3(kVecBlock), 0, stream, jd, (cplx*)vec_out, vec_stride, w_out);
+    SCINT_LAUNCH_CHECK();
     SCINT_HIP(hipStreamSynchronize(stream));
     return SCINT_OK;
 }

@@ -308,7 +308,7 @@ __device__ inline int shift_half(int i, int n) {
 }
 
 enum SrcMode { SRC_ARRAY = 0, SRC_SSPEC = 1, SRC_CS = 2, SRC_MODEL = 3, SRC_MULCONJ = 4, SRC_CONJ = 5,
-               SRC_ACF_IN = 6, SRC_POWER = 7 };
+               SRC_ACF_IN = 6, SRC_POWER = 7, SRC_CPAD = 8 };
 
 // Element (row, j) of the row-FFT input, j in [0, fft length).
 struct RowSource {
@@ -320,6 +320,7 @@ struct RowSource {
     // SRC_SSPEC (dynspec.py:3667-3685)
     WindowedValue wv; const double* m2; int nt_eff; int prewhite;
     // SRC_CS: np.pad(dspec, right, constant)  (ththmod.py:777-782): reuses wv.dyn / wv.nt
+    // SRC_CPAD: np.pad(x, right, 0) of a COMPLEX x[., wv.nt] = a (a visibility, ththmod.py:1313-1321): reuses a / wv.nt
     double pad;
     // SRC_MODEL: conj(ifftshift(recov)) -- real(ifft2(x)) == real(fft2(conj x))/(R C)
     int R, C;
@@ -350,6 +351,7 @@ struct RowSource {
                     v = mk(sspec_d(r + 1, j + 1) - sspec_d(r + 1, j) - sspec_d(r, j + 1) + sspec_d(r, j), 0.0);
                 break;
             case SRC_CS: v = mk(j < wv.nt ? wv.dyn[(int64_t)r * wv.nt + j] : pad, 0.0); break;
+            case SRC_CPAD: v = j < wv.nt ? a[(int64_t)r * wv.nt + j] : mk(0.0, 0.0); break;
             default: {  // SRC_MODEL
                 const int sr = shift_half(r, R), sc = shift_half(j, C);
                 v = conj(a[(int64_t)sr * C + sc]);
@@ -1098,6 +1100,31 @@ extern "C" int32_t scint_cs(const double* dspec, int64_t nf, int64_t nt, int64_t
     // rows >= nf are constant rows of pad_value: their FFT is C*pad at column 0
     return fft2_general(src, nf, pad_value * (double)C, R, C, sink, workspace, workspace_bytes, stream,
                         /*real_input=*/true);
+}
+
+// ------------------------------------------------------------------------------
+// scint_cs_complex_batch: the conjugate spectra of complex, ZERO-padded inputs (the visibilities of VLBI_chunk_retrieval,
+// ththmod.py:1313-1325): fftshift(fft2(np.pad(x, right/bottom, 0))) with the masked delay rows written as zero.  The rows
+// below the input are zero, so only nf row transforms are taken (fill0 = 0); the complex route of fft2_general, the sink of scint_cs.
+// ------------------------------------------------------------------------------
+extern "C" int32_t scint_cs_complex_batch(const scint_c128* xstack, int64_t n, int64_t nf, int64_t nt, int64_t npad,
+                                          const int64_t* mask_lohi, scint_c128* cs_stack, void* workspace,
+                                          size_t workspace_bytes, void* stream_) {
+    SCINT_REQUIRE(xstack && mask_lohi && cs_stack && workspace && n >= 1, "cs_complex_batch: null pointer or empty batch");
+    SCINT_REQUIRE(nf >= 1 && nt >= 1 && npad >= 0, "cs_complex_batch: bad shape");
+    hipStream_t stream = (hipStream_t)stream_;
+    const int64_t R = (npad + 1) * nf, C = (npad + 1) * nt;
+    SCINT_REQUIRE(R >= 2, "cs_complex_batch: need at least two delay rows");
+    for (int64_t k = 0; k < n; ++k) {
+        RowSource src{};
+        src.mode = SRC_CPAD; src.a = (const cplx*)xstack + k * nf * nt; src.wv.nt = (int)nt;
+        ColSink sink{};
+        sink.mode = SINK_CS; sink.out_c = (cplx*)cs_stack + k * R * C; sink.ld = (int)C;
+        sink.mask_lo = (int)mask_lohi[2 * k]; sink.mask_hi = (int)mask_lohi[2 * k + 1]; sink.incoherent = 0;
+        const int32_t rc = fft2_general(src, nf, 0.0, R, C, sink, workspace, workspace_bytes, stream);
+        if (rc != SCINT_OK) return rc;
+    }
+    return SCINT_OK;
 }
 
 // ------------------------------------------------------------------------------

@@ -5,8 +5,10 @@
 // falls in is decided by a floor / an ordered comparison of float64 expressions,
 // and the reference evaluates those expressions with one IEEE rounding per NumPy
 // ufunc.  A fused multiply-add would flip pixels.
+#include <algorithm>
 #include <map>
 #include <type_traits>
+#include <vector>
 #include <float.h>
 #include <limits.h>
 #include <math.h>
@@ -87,6 +89,82 @@ int32_t launch_gather(const cplx* cs, const GeomDev& g, const double* th_cents, 
     profiler().end(kProfGather, slot, stream);
     SCINT_LAUNCH_CHECK();
     return SCINT_OK;
+}
+
+// ------------------------------------------------------------------------------
+// composite theta-theta of VLBI_chunk_retrieval (ththmod.py:1292-1362)
+// ------------------------------------------------------------------------------
+// Spectrum (d1, d2) of a chunk -- station pair (d1, d1 + d2), d2 = 0: the dynamic spectrum of station d1 -- gives the N x N
+// reduced theta-theta T of its conjugate spectrum; the composite [n_dish N]^2 holds T in block (d1 + d2, d1) and conj(T^T) in
+// block (d1, d1 + d2) (ththmod.py:1352-1362).  One 32 x 32 tile of one spectrum per workgroup, as thth_gather_kernel: a CS pixel
+// is read once and feeds both blocks, the mirrored one through an LDS transpose so that both stores are coalesced row segments.
+// d2 = 0 is the Hermitian arithmetic of thth_map (ththmod.py:108-114: upper triangle, mirrored, diagonal and FULL-grid
+// anti-diagonal zeroed, nan_to_num) written to the one diagonal block; d2 > 0 is hermetian=False: the plain gather, nothing
+// zeroed, no nan_to_num.  The crop (keep) is the chunk's: it depends on eta, edges and tau only (ththmod.py:148-160).
+__global__ void __launch_bounds__(256)
+vlbi_gather_kernel(const VlbiJob* __restrict__ jobs, const GeomDev* __restrict__ geoms) {
+    __shared__ cplx tile[kTile][kTile + 1];
+    const VlbiJob job = jobs[blockIdx.z];
+    const int N = job.n;
+    const int I0 = blockIdx.y * kTile, J0 = blockIdx.x * kTile;
+    if (I0 >= N || J0 >= N) return;
+    const bool herm = job.rb == job.cb;
+    if (herm && J0 < I0) return;
+    const GeomDev g = geoms[job.geom];
+    const double* __restrict__ th = job.th;
+    const int64_t ld = job.ld;
+    cplx* __restrict__ lower = job.comp + ((int64_t)job.rb * N) * ld + (int64_t)job.cb * N;   // block (d1 + d2, d1) <- T
+    cplx* __restrict__ upper = job.comp + ((int64_t)job.cb * N) * ld + (int64_t)job.rb * N;   // block (d1, d1 + d2) <- conj(T^T)
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+    const int j = J0 + tx;
+    const int kj = j < N ? job.keep[j] : 0;
+    const double th_j = j < N ? th[kj] : 0.0;
+
+    if (!herm) {
+        for (int r = ty; r < kTile; r += 8) {
+            const int i = I0 + r;
+            cplx v = mk(0.0, 0.0);
+            if (i < N && j < N) {
+                v = thth_value(job.cs, g, job.eta, job.two_eta, th[job.keep[i]], th_j);
+                lower[(int64_t)i * ld + j] = v;
+            }
+            tile[r][tx] = v;
+        }
+        __syncthreads();
+        // upper[J0 + a][I0 + b] = conj(T[I0 + b][J0 + a]), b fastest
+        for (int a = ty; a < kTile; a += 8) {
+            const int row = J0 + a, col = I0 + tx;
+            if (row < N && col < N) upper[(int64_t)row * ld + col] = conj(tile[tx][a]);
+        }
+        return;
+    }
+
+    const bool diag_tile = (I0 == J0);
+    for (int r = ty; r < kTile; r += 8) {
+        const int i = I0 + r;
+        cplx v = mk(0.0, 0.0);
+        if (i < N && j < N && i < j) {
+            const int ki = job.keep[i];
+            v = thth_value(job.cs, g, job.eta, job.two_eta, th[ki], th_j);
+            if ((int64_t)ki + kj == job.M - 1) v = mk(0.0, 0.0);     // anti-diagonal of the FULL matrix (ththmod.py:113)
+            v = mk(nan_to_num(v.x), nan_to_num(v.y));
+        }
+        tile[r][tx] = v;
+        if (!diag_tile && i < N && j < N) lower[(int64_t)i * ld + j] = v;
+    }
+    __syncthreads();
+    if (diag_tile) {
+        for (int r = ty; r < kTile; r += 8) {
+            const int i = I0 + r;
+            if (i < N && j < N)
+                lower[(int64_t)i * ld + j] = (r < tx) ? tile[r][tx] : (r > tx ? conj(tile[tx][r]) : mk(0.0, 0.0));
+        }
+    } else {
+        for (int a = ty; a < kTile; a += 8) {
+            const int row = J0 + a, col = I0 + tx;
+            if (row < N && col < N) lower[(int64_t)row * ld + col] = conj(tile[tx][a]);
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------
@@ -1404,6 +1482,81 @@ extern "C" int32_t scint_thth_map(const scint_c128* cs, const scint_cs_geom* geo
     job.out = (cplx*)thth_out;
     job.ld = N;
     return launch_gather((const cplx*)cs, to_dev(*geom), th_cents, M, job, stream);
+}
+
+// ---- scint_vlbi_composite: the composite theta-theta matrices of a group of VLBI chunks ------------------------------------
+extern "C" int32_t scint_vlbi_composite_workspace_bytes(int64_t nchunk, int64_t n_dish, size_t* bytes) {
+    SCINT_REQUIRE(bytes && nchunk >= 1 && n_dish >= 1, "vlbi_composite_workspace_bytes: bad arguments");
+    const int64_t nspec = n_dish * (n_dish + 1) / 2;
+    *bytes = align_up(sizeof(VlbiJob) * (size_t)(nchunk * nspec), 256) + align_up(sizeof(GeomDev) * (size_t)nchunk, 256) + 256;
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_vlbi_composite(const scint_c128* cs_stack, int64_t cs_stride, const int64_t* cs_slot,
+                                        const scint_cs_geom* geoms, const double* th_stack, int64_t M,
+                                        const int32_t* keep_idx, const int32_t* keep_n, const double* etas,
+                                        int64_t nchunk, int64_t n_dish, scint_c128* comp_out, int64_t comp_stride,
+                                        void* workspace, size_t workspace_bytes, void* stream_) {
+    SCINT_REQUIRE(cs_stack && cs_slot && geoms && th_stack && keep_idx && keep_n && etas && comp_out && workspace,
+                  "vlbi_composite: null pointer");
+    SCINT_REQUIRE(nchunk >= 1 && n_dish >= 1 && M >= 1, "vlbi_composite: bad arguments");
+    hipStream_t stream = (hipStream_t)stream_;
+    size_t need = 0;
+    scint_vlbi_composite_workspace_bytes(nchunk, n_dish, &need);
+    if (workspace_bytes < need) { set_error("scint: vlbi_composite workspace too small"); return SCINT_E_WORKSPACE; }
+    const int64_t nspec = n_dish * (n_dish + 1) / 2;
+    std::vector<VlbiJob> jobs;
+    std::vector<GeomDev> gd((size_t)nchunk);
+    int64_t nmax = 0;
+    for (int64_t k = 0; k < nchunk; ++k) {
+        const int64_t N = keep_n[k], S = n_dish * N;
+        SCINT_REQUIRE(N >= 0 && N <= M && S * S <= comp_stride, "vlbi_composite: crop larger than the grid or the composite's slot");
+        SCINT_REQUIRE(geoms[k].ntau >= 1 && geoms[k].nfd >= 1 && geoms[k].ntau * geoms[k].nfd <= cs_stride,
+                      "vlbi_composite: spectrum larger than its slot");
+        gd[(size_t)k] = to_dev(geoms[k]);
+        if (N == 0) continue;
+        nmax = std::max(nmax, N);
+        for (int64_t d1 = 0; d1 < n_dish; ++d1)
+            for (int64_t d2 = 0; d2 < n_dish - d1; ++d2) {
+                // position of the pair in the reference's list [I1, V12, ..., V1N, I2, V23, ..., IN] (ththmod.py:1345-1349)
+                const int64_t idx = nspec - ((n_dish - d1) * (n_dish - d1 + 1)) / 2 + d2;
+                const int64_t slot = cs_slot[k * nspec + idx];
+                SCINT_REQUIRE(slot >= 0, "vlbi_composite: negative spectrum slot");
+                VlbiJob jb;
+                jb.cs = (const cplx*)cs_stack + slot * cs_stride;
+                jb.th = th_stack + k * M;
+                jb.keep = keep_idx + k * M;
+                jb.comp = (cplx*)comp_out + k * comp_stride;
+                jb.ld = S;
+                jb.eta = etas[k]; jb.two_eta = 2 * etas[k];
+                jb.n = (int32_t)N; jb.geom = (int32_t)k; jb.rb = (int32_t)(d1 + d2); jb.cb = (int32_t)d1; jb.M = (int32_t)M; jb.pad = 0;
+                jobs.push_back(jb);
+            }
+    }
+    if (jobs.empty()) return SCINT_OK;
+    const unsigned nt = (unsigned)ceil_div(nmax, kTile);
+    SCINT_REQUIRE(nt <= 65535, "vlbi_composite: grid too large");
+    VlbiJob* jobs_dev = (VlbiJob*)workspace;
+    GeomDev* geoms_dev = (GeomDev*)((char*)workspace + align_up(sizeof(VlbiJob) * (size_t)(nchunk * nspec), 256));
+    // The job tables are host vectors: whatever happens after the first copy is queued, the stream is drained before they go
+    // away -- on the error paths too.
+    auto queue = [&]() -> int32_t {
+        SCINT_HIP(hipMemcpyAsync(jobs_dev, jobs.data(), sizeof(VlbiJob) * jobs.size(), hipMemcpyHostToDevice, stream));
+        SCINT_HIP(hipMemcpyAsync(geoms_dev, gd.data(), sizeof(GeomDev) * gd.size(), hipMemcpyHostToDevice, stream));
+        for (size_t j0 = 0; j0 < jobs.size(); j0 += 65535) {
+            const unsigned nz = (unsigned)std::min<size_t>(65535, jobs.size() - j0);
+            const int slot = profiler().begin(kProfGather, stream);
+            hipLaunchKernelGGL(vlbi_gather_kernel, dim3(nt, nt, nz), dim3(256), 0, stream, jobs_dev + j0, geoms_dev);
+            profiler().end(kProfGather, slot, stream);
+            SCINT_LAUNCH_CHECK();
+        }
+        return SCINT_OK;
+    };
+    const int32_t rc = queue();
+    const hipError_t se = hipStreamSynchronize(stream);
+    if (rc != SCINT_OK) return rc;
+    SCINT_HIP(se);
+    return SCINT_OK;
 }
 
 extern "C" int32_t scint_rev_map_workspace_bytes(size_t* bytes) {

@@ -157,6 +157,17 @@ struct ThinJob {
 int32_t launch_thin_gather(const ThinJob* jobs_dev, const ThinGeomDev* geoms_dev, int64_t njobs, int64_t max_domain,
                            hipStream_t stream);
 
+// One spectrum of one chunk of the VLBI composite (thth.hip, vlbi_gather_kernel): station pair (cb, rb), rb >= cb.
+struct VlbiJob {
+    const cplx* cs;          // the spectrum's conjugate spectrum [ntau, nfd]
+    const double* th;        // the chunk's theta centres [M]
+    const int32_t* keep;     // the chunk's crop: N ascending indices into th
+    cplx* comp;              // the chunk's composite [n_dish N, ld]
+    int64_t ld;
+    double eta, two_eta;
+    int32_t n, geom, rb, cb, M, pad;   // N; index of the chunk's geometry; row and column block of T
+};
+
 // One theta-theta matrix to build: curvature, crop and destination.
 struct GatherJob {
     double eta, two_eta;     // eta and 2*eta (ththmod.py:95, 107)

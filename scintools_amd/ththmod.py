@@ -21,6 +21,9 @@ two_curve_map      ththmod.py:1557-1636   scint_two_curve_map
 singularvalue_calc ththmod.py:496-513     scint_sv_sweep_multi (one map)
 single_search_thin ththmod.py:516-712     scint_cs + scint_sv_sweep_multi (+ SciPy fit)
 sv_sweep_multi     (fit_thetatheta thin)  scint_sv_sweep_multi
+VLBI_chunk_retrieval ththmod.py:1223-1387 scint_cs_batch + scint_cs_complex_batch +
+                                          scint_vlbi_composite + scint_eigh_top_batch +
+                                          scint_retrieval_tail
 =================  =====================  ========================================
 
 ``tau, fd, eta, edges`` may be bare numbers (us, mHz, s**3, mHz) or, when astropy
@@ -1197,6 +1200,260 @@ def single_chunk_retrieval(params):
         print(exc, flush=True)
         model_E = np.zeros(dspec2.shape, dtype=complex)
     return (model_E, idx_f, idx_t)
+
+
+# ----------------------------------------------------------------------------
+# multi-station (VLBI) phase retrieval (ththmod.py:1223-1387)
+# ----------------------------------------------------------------------------
+def _vlbi_spectrum_index(n_dish, d1, d2):
+    """Position of station pair (d1, d1 + d2) in [I1, V12, ..., V1N, I2, V23, ..., IN] (ththmod.py:1345-1349)."""
+    return (n_dish * (n_dish + 1)) // 2 - ((n_dish - d1) * (n_dish - d1 + 1)) // 2 + d2
+
+
+def _vlbi_gather_raises(grid, eta):
+    """True where NumPy's fancy index of thth_map (ththmod.py:104) raises IndexError: a kept point (0 < tau_inv < ntau) whose
+    Doppler index lies below -len(fd).  Only edges wider than 1.5 times the Doppler span can reach such an index; the M x M
+    index maps are formed (on the host, the reference's expressions) only then."""
+    g, th = grid.geom, grid.th_cents
+    if not np.floor(((th.min() - th.max()) - g.fd0 + g.dfd / 2) / g.dfd) < -g.nfd:
+        return False
+    th1 = np.ones((th.shape[0], th.shape[0])) * th
+    th2 = th1.T
+    tau_inv = (((eta * (th1**2 - th2**2)) - g.tau0 + g.dtau / 2) // g.dtau).astype(int)
+    fd_inv = (((th1 - th2) - g.fd0 + g.dfd / 2) // g.dfd).astype(int)
+    return bool(((tau_inv > 0) * (tau_inv < g.ntau) * (fd_inv < -g.nfd)).any())
+
+
+def _vlbi_composites_dev(stack_t, slots, grids, etas, keeps, n_dish, S=None):
+    """The composite theta-theta of every chunk of a group (scint_vlbi_composite).  stack_t: device [nslot, ntau, nfd] conjugate
+    spectra; slots: int [n, nspec], the slot of spectrum idx of chunk k (the reference's list order); grids / etas / keeps: per
+    chunk its _Grid, curvature and the kept indices of thth_redmap's crop.  Returns the device tensor [n, S * S]: chunk k's dense
+    [n_dish N_k, n_dish N_k] composite sits at the start of row k (S = n_dish max N_k unless given larger)."""
+    lib = _lib.load()
+    n, M = len(grids), grids[0].M
+    nspec = n_dish * (n_dish + 1) // 2
+    slots = np.ascontiguousarray(slots, dtype=np.int64).reshape(n, nspec)
+    if slots.min() < 0 or slots.max() >= stack_t.shape[0]:
+        raise ValueError("spectrum slot outside the stack")
+    etas = np.ascontiguousarray(etas, dtype=np.float64)
+    keep_n = np.ascontiguousarray([k_.shape[0] for k_ in keeps], dtype=np.int32)
+    if S is None:
+        S = n_dish * int(keep_n.max())
+    R, C = (int(v) for v in stack_t.shape[1:])
+    th_all, keep_all = np.zeros((n, M)), np.zeros((n, M), dtype=np.int32)
+    for j in range(n):
+        if grids[j].M != M or (grids[j].geom.ntau, grids[j].geom.nfd) != (R, C) or (keep_n[j] and int(keeps[j].max()) >= M):
+            raise ValueError("chunk %d: grid does not match the batch" % j)
+        th_all[j] = grids[j].th_cents
+        keep_all[j, :keep_n[j]] = keeps[j]
+    th_t, keep_t = _dv.to_device(th_all, torch.float64), _dv.to_device(keep_all, torch.int32)
+    comp = torch.empty((n, S * S), dtype=torch.complex128, device=stack_t.device)
+    geoms = (_lib.CsGeom * n)(*[g_.geom for g_ in grids])
+    need = ctypes.c_size_t()
+    _lib.check(lib.scint_vlbi_composite_workspace_bytes(n, n_dish, ctypes.byref(need)), "vlbi_composite_workspace_bytes")
+    ws = workspace.get(need.value)
+    _lib.check(lib.scint_vlbi_composite(ptr(stack_t), R * C, slots.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), geoms, ptr(th_t), M,
+                                        ptr(keep_t), keep_n.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                        etas.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n, n_dish, ptr(comp), S * S,
+                                        ptr(ws), ws.numel(), stream_ptr()), "scint_vlbi_composite")
+    return comp
+
+
+def vlbi_retrieval_batch(chunks, npad, n_dish, tauMask, verbose=False, group_bytes=None, out_device=False,
+                         tol=DEFAULT_TOL, max_iter=DEFAULT_MAX_ITER, info=None):
+    """Multi-station phase retrieval of MANY chunks of one shape: VLBI_chunk_retrieval (ththmod.py:1223-1387) for all of them
+    with everything between the input pixels and the wavefields on the device.
+
+    chunks: list of (dspec2_list, edges, time, freq, eta); dspec2_list holds the n_dish (n_dish + 1) / 2 spectra of the chunk,
+    each [nf, nt], in the reference's order [I1, V12, ..., V1N, I2, V23, ..., IN] (dynamic spectra real, visibilities complex).
+    Returns complex [nchunk, n_dish, nf, nt] (a device tensor with ``out_device``): the wavefield of every station.
+
+    Per group of chunks: the dynamic spectra's conjugate spectra (mean-padded, scint_cs_batch) and the visibilities'
+    (zero-padded complex, scint_cs_complex_batch) in one device stack; every chunk's composite theta-theta -- block
+    (d1 + d2, d1) the reduced theta-theta of pair (d1, d1 + d2), block (d1, d1 + d2) its conjugate transpose, Hermitian forcing
+    on the dynamic spectra only -- written by ONE gather (scint_vlbi_composite) as dense matrices; their dominant eigenpairs by
+    the batched Lanczos of scint_eigh_top_batch; then per chunk and station the row conj(V[d N:(d + 1) N]) sqrt(w) through
+    scint_retrieval_tail (the stations of a chunk share the back-map's pair counts).  Groups are sized like
+    :func:`chunk_retrieval_batch`'s: the device bytes of a chunk (its spectra, its composite and the Lanczos vectors) against
+    ``group_bytes`` (default ``RETRIEVAL_GROUP_BYTES``).
+
+    Like the reference function, and unlike single_chunk_retrieval, nothing is caught: a chunk whose crop keeps fewer than two
+    centres raises IndexError (the reference's thth_redmap indexes an empty edges_red, ththmod.py:163), an eigen-solve that
+    fails raises ArithmeticError, and either ends the whole call.
+
+    Phases: the eigenvector has ONE arbitrary global phase per chunk, common to its stations; the phases BETWEEN stations are
+    determined, and they come out consistent with the visibilities under the convention V_ab = E_a conj(E_b).
+
+    ``info`` (a dict, tests and tools): receives ``composites`` (per chunk the host copy of its [n_dish N, n_dish N] composite),
+    ``w`` and ``iters`` (eigenvalue and Lanczos steps per chunk), ``groups`` (the number of groups the chunks went in)."""
+    n_dish = int(n_dish)
+    if n_dish < 1:
+        raise ValueError("n_dish must be at least 1")
+    nspec = n_dish * (n_dish + 1) // 2
+    nvis = nspec - n_dish
+    dyn_idx = [_vlbi_spectrum_index(n_dish, d, 0) for d in range(n_dish)]
+    vis_idx = [i for i in range(nspec) if i not in dyn_idx]
+    if len(chunks) == 0:
+        return np.zeros((0, n_dish, 0, 0), dtype=complex)
+    for k, c in enumerate(chunks):
+        if len(c[0]) != nspec:
+            raise ValueError("chunk %d: %d spectra for n_dish = %d (%d expected)" % (k, len(c[0]), n_dish, nspec))
+    nf, nt = np.asarray(chunks[0][0][0]).shape
+    R, C = (npad + 1) * nf, (npad + 1) * nt
+    _check_sweep_cs(R, C)
+    dev = require_gpu()
+    lib = _lib.load()
+    mask_us = float(units.strip(tauMask, "tauMask", "us", warn=False))
+    out = torch.zeros((len(chunks), n_dish, nf, nt), dtype=torch.complex128, device=dev) if out_device else \
+        np.zeros((len(chunks), n_dish, nf, nt), dtype=complex)
+
+    # host preparation of every chunk (grids are shared between chunks with equal axes and edges, as in chunk_retrieval_batch)
+    grid_cache, prep = {}, []
+    for k, (dlist, edges, time, freq, eta) in enumerate(chunks):
+        time_v = np.asarray(units.strip(time, "time2", "s", warn=False))
+        freq_v = np.asarray(units.strip(freq, "freq2", "MHz", warn=False))
+        edges_v = np.asarray(units.strip(edges, "edges", "mHz", warn=False))
+        key = (time_v.shape[0], float(time_v[1] - time_v[0]), freq_v.shape[0], float(freq_v[1] - freq_v[0]), edges_v.tobytes())
+        grid = grid_cache.get(key)
+        if grid is None:
+            grid = _Grid(fft_axis(freq_v, 1.0, npad), fft_axis(time_v, 1000.0, npad), edges_v)
+            grid_cache[key] = grid
+        if (grid.geom.ntau, grid.geom.nfd) != (R, C) or (prep and grid.M != prep[0][0].M):
+            raise ValueError("chunk %d: axes or edges do not match the chunk shape (%d, %d)" % (k, nf, nt))
+        for x in dlist:
+            if np.shape(x) != (nf, nt):
+                raise ValueError("chunk %d: a spectrum of shape %s in a batch of (%d, %d)" % (k, np.shape(x), nf, nt))
+        e = _eta_float(eta)
+        keep = grid.keep(e)
+        if keep.shape[0] < 2:
+            raise IndexError("chunk %d: the crop of thth_redmap keeps %d theta centres (index 0 is out of bounds for edges_red, "
+                             "ththmod.py:163)" % (k, keep.shape[0]))
+        if _vlbi_gather_raises(grid, e):
+            raise IndexError("chunk %d: theta-theta gather index out of bounds for the conjugate spectrum" % k)
+        prep.append((grid, e, keep))
+    M = prep[0][0].M
+    nmax = max(p_[2].shape[0] for p_ in prep)
+    S = n_dish * nmax
+    per_chunk = 16 * (nspec * R * C + S * S + (min(max_iter, S) + 4) * S) + 16 * nspec * nf * nt
+    per_group = int(min(65535, max(1, (RETRIEVAL_GROUP_BYTES if group_bytes is None else group_bytes) // per_chunk)))
+
+    for g0 in range(0, len(chunks), per_group):
+        group = chunks[g0:g0 + per_group]
+        n = len(group)
+        grids = [prep[g0 + j][0] for j in range(n)]
+        etas = np.ascontiguousarray([prep[g0 + j][1] for j in range(n)], dtype=np.float64)
+        keep_n = np.ascontiguousarray([prep[g0 + j][2].shape[0] for j in range(n)], dtype=np.int32)
+        # one upload each way: dynamic spectra [n * n_dish], visibilities [n * nvis]; padding value = the spectrum's own mean
+        d_all = np.empty((n * n_dish, nf, nt))
+        v_all = np.empty((n * nvis, nf, nt), dtype=complex)
+        pads = np.empty(n * n_dish)
+        for j, c in enumerate(group):
+            for q, i in enumerate(dyn_idx):
+                a = np.asarray(c[0][i])
+                a = np.asarray(a.real if np.iscomplexobj(a) else a, dtype=float)
+                d_all[j * n_dish + q] = a
+                pads[j * n_dish + q] = float(a.mean())                            # ththmod.py:1303
+            for q, i in enumerate(vis_idx):
+                v_all[j * nvis + q] = np.asarray(c[0][i])
+        lohi = np.zeros((n, 2), dtype=np.int64)
+        for j in range(n):
+            sel = np.nonzero(np.abs(grids[j].tau) < mask_us)[0]                   # ththmod.py:1308 / 1325
+            if sel.size:
+                lohi[j] = (int(sel[0]), int(sel[-1]) + 1)
+                if lohi[j, 1] - lohi[j, 0] != sel.size:
+                    raise ValueError("tau mask is not a contiguous block of delays")
+        stack = torch.empty((n * nspec, R, C), dtype=torch.complex128, device=dev)   # slots: the dynamic spectra, then the visibilities
+        need = ctypes.c_size_t()
+        _lib.check(lib.scint_cs_workspace_bytes(nf, nt, npad, ctypes.byref(need)), "cs_workspace_bytes")
+        ws = workspace.get(need.value)
+        d_t = _dv.to_device(d_all, torch.float64)
+        lohi_d = np.ascontiguousarray(np.repeat(lohi, n_dish, axis=0))
+        _lib.check(lib.scint_cs_batch(ptr(d_t), n * n_dish, nf, nt, npad, pads.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                      lohi_d.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), 0, ptr(stack), ptr(ws), ws.numel(),
+                                      stream_ptr()), "scint_cs_batch")
+        v_t = None
+        if nvis:
+            v_t = _dv.to_device(v_all, torch.complex128)
+            lohi_v = np.ascontiguousarray(np.repeat(lohi, nvis, axis=0))
+            _lib.check(lib.scint_cs_complex_batch(ptr(v_t), n * nvis, nf, nt, npad, lohi_v.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                                  ptr(stack[n * n_dish:]), ptr(ws), ws.numel(), stream_ptr()), "scint_cs_complex_batch")
+        slots = np.empty((n, nspec), dtype=np.int64)
+        for q, i in enumerate(dyn_idx):
+            slots[:, i] = np.arange(n) * n_dish + q
+        for q, i in enumerate(vis_idx):
+            slots[:, i] = n * n_dish + np.arange(n) * nvis + q
+        comp = _vlbi_composites_dev(stack, slots, grids, etas, [prep[g0 + j][2] for j in range(n)], n_dish, S)
+        # dominant ('LA') eigenpair of every composite, started from the zero-theta row of the first station's block row
+        sizes = np.ascontiguousarray(n_dish * keep_n, dtype=np.int32)
+        start = np.ascontiguousarray(keep_n // 2, dtype=np.int32)
+        _lib.check(lib.scint_eigh_top_batch_workspace_bytes(S, max_iter, n, ctypes.byref(need)), "eigh_top_batch_workspace_bytes")
+        ws = workspace.get(need.value)
+        w_t = empty((n,), torch.float64)
+        V_t = torch.zeros((n, S), dtype=torch.complex128, device=dev)
+        st_t = torch.zeros((2, n), dtype=torch.int32, device=dev)
+        _lib.check(lib.scint_eigh_top_batch(ptr(comp), S * S, sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                            start.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n, tol, max_iter, ptr(w_t), ptr(V_t), S,
+                                            ptr(st_t[0]), ptr(st_t[1]), ptr(ws), ws.numel(), stream_ptr()), "scint_eigh_top_batch")
+        st = st_t.cpu().numpy()
+        if (st[0] != 0).any():
+            j = int(np.nonzero(st[0])[0][0])
+            raise ArithmeticError("chunk %d: top-eigenpair iteration of the composite failed (status %d, %d steps)"
+                                  % (g0 + j, st[0][j], st[1][j]))
+        w, V = w_t.cpu().numpy(), V_t.cpu().numpy()
+        if info is not None:
+            comp_h = comp.cpu().numpy()
+            info.setdefault("composites", []).extend(comp_h[j, :int(sizes[j]) ** 2].reshape(int(sizes[j]), int(sizes[j])).copy() for j in range(n))
+            info.setdefault("w", []).extend(float(x) for x in w)
+            info.setdefault("iters", []).extend(int(x) for x in st[1])
+            info["groups"] = info.get("groups", 0) + 1
+        rows_all, th_rows = np.zeros((n * n_dish, M), dtype=complex), np.zeros((n * n_dish, M))
+        th_cache = {}
+        for j in range(n):
+            N = int(keep_n[j])
+            keep = prep[g0 + j][2]
+            tkey = (id(grids[j]), int(keep[0]), N) if N == int(keep[-1]) - int(keep[0]) + 1 else None
+            th_red = th_cache.get(tkey) if tkey is not None else None
+            if th_red is None:
+                th_red = _theta_centres(grids[j].edges_red(keep))
+                if tkey is not None:
+                    th_cache[tkey] = th_red
+            with np.errstate(invalid="ignore"):
+                amp = np.sqrt(w[j])                                                # ththmod.py:1376
+            for d in range(n_dish):
+                rows_all[j * n_dish + d, :N] = np.conjugate(V[j, d * N:(d + 1) * N]) * amp
+                th_rows[j * n_dish + d, :N] = th_red
+        out_t = _retrieval_tail_dev(rows_all, th_rows, np.repeat(keep_n, n_dish), None, [g_ for g_ in grids for _ in range(n_dish)],
+                                    np.repeat(etas, n_dish), nf, nt)
+        if verbose:
+            for j in range(n):
+                print("Chunk %d success" % (g0 + j), flush=True)
+        if out_device:
+            out[g0:g0 + n] = out_t.view(n, n_dish, nf, nt)
+        else:
+            out[g0:g0 + n] = out_t.cpu().numpy().reshape(n, n_dish, nf, nt)
+        del stack, comp, V_t, out_t, d_t, v_t, ws
+    return out
+
+
+def VLBI_chunk_retrieval(params):
+    """Phase retrieval on one time/frequency chunk from the dynamic spectra and visibilities of several stations
+    (ththmod.py:1223-1387): the one-chunk case of :func:`vlbi_retrieval_batch`.
+
+    params = (dspec2_list, edges, time, freq, eta, idx_t, idx_f, npad, n_dish, tauMask, verbose) as in the reference;
+    dspec2_list is ordered [I1, V12, ..., V1N, I2, V23, ..., IN].  time, freq, eta, edges and tauMask may be plain numbers
+    (s, MHz, s**3, mHz, us) or Quantities.  Returns (model_E, idx_f, idx_t) with model_E a list of n_dish complex [nf, nt]
+    arrays.  As in the reference there is no try/except: errors propagate.
+
+    The wavefields share ONE arbitrary global phase (the eigenvector's); the phases between stations are determined.  They are
+    consistent with the inputs when the visibilities follow V_ab = E_a conj(E_b) (and I_a = |E_a|**2): station b's wavefield then
+    carries its phase offset against station a with the sign the data has."""
+    dspec2_list, edges, time, freq, eta, idx_t, idx_f, npad, n_dish, tauMask, verbose = params
+    if verbose:
+        print("Starting Chunk %s-%s" % (idx_f, idx_t), flush=True)
+    E = vlbi_retrieval_batch([(dspec2_list, edges, time, freq, eta)], int(npad), int(n_dish), tauMask)
+    if verbose:
+        print("Chunk %s-%s success" % (idx_f, idx_t), flush=True)
+    return ([E[0, d] for d in range(int(n_dish))], idx_f, idx_t)
 
 
 def mask_func(w):
