@@ -344,6 +344,30 @@ int32_t scint_chunk_cut(const double* dyn, int64_t nf, int64_t nt, const int32_t
                         int64_t cwf, int64_t cwt, int32_t colmajor, double* chunks_out, double* pad_out, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* ---- the fitted mosaics (ththmod.py:1708-2310: rotMos / rotFit / rotDer, fullMos / fullMosFit / fullMosGrad / fullMosHess) ----
+ * W = sum_k A_k exp(i phi_k) mask_k (.) chunk_k over the stack `chunks` [ncf * nct][cwf][cwt] in half-overlapping windows (sizes
+ * even along an axis of several chunks), tapers rows[4][cwf] / cols[4][cwt] as above.  coef: DEVICE [ncf * nct][3] = amplitude,
+ * then real and imaginary part of exp(1j * phase) as the host's NumPy evaluated it (chunk 0: exp(0j)).  full = 0: rotMos (the
+ * amplitudes are not read) with the objective -sum |W|^2; full = 1: fullMos with nansum(((|W|^2 - dspec) / noise)^2), dspec and
+ * noise DEVICE [F][T] (the mosaic's extent, F = (ncf - 1) (cwf / 2) + cwf).
+ * scint_mosaic_fit_eval: W [F][T] <- the mosaic, every pixel's 1-4 terms added in the reference's order and evaluated as NumPy
+ * does (numpy_fused bit 0 as for scint_mosaic_add): equal to the host loop bit for bit.  want = 0: that is all (dspec, noise, out
+ * and the workspace may be null); 1: out[0] <- the objective; 2: also out[1 + k] <- d/d phi_k and, full, out[1 + n + k] <-
+ * d/d A_k for every chunk k (k = 0 included: the caller drops its phase).  out: DEVICE [1 + 2 n].  Three launches, fixed-order
+ * sums, no floating-point atomics: equal inputs give equal bits.
+ * scint_mosaic_fit_hess: H [2 n - 1][2 n - 1] <- fullMosHess at the W that scint_mosaic_fit_eval formed from the same coef
+ * (parameters: phases of chunks 1 .. n - 1, then the n amplitudes); numpy.sum, so a NaN or zero of dspec / noise shows in the
+ * entries it touches; zero outside the neighbour band; exactly symmetric (where the reference writes an entry from the visits
+ * (N, M) and (M, N), the later one's value, as there). */
+int32_t scint_mosaic_fit_workspace_bytes(int64_t ncf, int64_t nct, int64_t cwf, int64_t cwt, size_t* bytes /*HOST*/);
+int32_t scint_mosaic_fit_eval(const scint_c128* chunks, int64_t ncf, int64_t nct, int64_t cwf, int64_t cwt, const double* rows,
+                              const double* cols, const double* coef, int32_t full, int32_t numpy_fused, const double* dspec,
+                              const double* noise, scint_c128* W, int32_t want, double* out, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int32_t scint_mosaic_fit_hess(const scint_c128* chunks, int64_t ncf, int64_t nct, int64_t cwf, int64_t cwt, const double* rows,
+                              const double* cols, const double* coef, const double* dspec, const double* noise,
+                              const scint_c128* W, double* H, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the per-chunk steps of Dynspec.thetatheta_chunks, a whole group of chunks per call (dynspec.py:1765-1826; the reference
  * maps single_chunk_retrieval, ththmod.py:1390-1476, over the chunks) --------------------------------------------------------
  * scint_cs_batch: scint_cs of every chunk of dstack [n][nf][nt] into cs_stack [n][R][C]; pads (HOST [n]) the padding values,

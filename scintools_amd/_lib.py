@@ -93,6 +93,9 @@ _SIGNATURES = {
     "scint_mosaic_phase": ([_P, c_int64, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int32, _P, c_size_t, _P, _P], c_int32),
     "scint_mosaic_add": ([_P, c_int64, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int32, POINTER(c_double), _P], c_int32),
     "scint_chunk_cut": ([_P, c_int64, c_int64, _P, _P, c_int64, c_int64, c_int64, c_int32, _P, _P, _P, c_size_t, _P], c_int32),
+    "scint_mosaic_fit_workspace_bytes": ([c_int64, c_int64, c_int64, c_int64, POINTER(c_size_t)], c_int32),
+    "scint_mosaic_fit_eval": ([_P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, c_int32, c_int32, _P, _P, _P, c_int32, _P, _P, c_size_t, _P], c_int32),
+    "scint_mosaic_fit_hess": ([_P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P], c_int32),
     "scint_cs_batch": ([_P, c_int64, c_int64, c_int64, c_int64, POINTER(c_double), POINTER(c_int64), c_int32, _P, _P, c_size_t, _P], c_int32),
     "scint_cs_complex_batch": ([_P, c_int64, c_int64, c_int64, c_int64, POINTER(c_int64), _P, _P, c_size_t, _P], c_int32),
     "scint_vlbi_composite_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),

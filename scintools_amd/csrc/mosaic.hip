@@ -541,3 +541,281 @@ extern "C" int32_t scint_retrieval_tail(const scint_c128* rows, const double* th
     }
     return SCINT_OK;
 }
+
+// ---- the fitted mosaics (ththmod.py:1708-2310: rotMos / rotFit / rotDer, fullMos / fullMosFit / fullMosGrad / fullMosHess) ------
+// W = sum_k A_k e^{i phi_k} mask_k (.) chunk_k in half-overlapping windows, every phase (and amplitude) a free parameter.  The
+// reference rebuilds every taper and walks all chunks in Python for each objective, gradient and Hessian; here the stack stays in
+// HBM and one evaluation is three launches:
+//   (1) the mosaic as a GATHER: one thread per output pixel adds its 1-4 terms in the reference's order (chunks by cf, then ct),
+//       each term as NumPy evaluates it -- so W equals the host loop bit for bit -- and the objective's summand of that pixel goes
+//       into a per-workgroup partial;
+//   (2) per chunk, kFitBlocks(window) workgroups form the partial sums of its gradient entries over its window;
+//   (3) one launch adds the partials in a fixed order.
+// No floating-point atomics anywhere: the same inputs give the same bits.  The Hessian is one job per (chunk, neighbour) pair.
+namespace scint {
+
+struct FitArgs {
+    const cplx* chunks; int ncf, nct, cwf, cwt, hf, ht;    // the stack [ncf * nct][cwf][cwt]; chunk (cf, ct)'s window starts at (cf hf, ct ht)
+    int64_t F, T;                                           // the mosaic's extent
+    const double* rows; const double* cols;                 // tapers [4][cwf], [4][cwt] (MosaicArgs)
+    const double* coef;                                     // [n][3]: amplitude, then exp(1j * phase) as NumPy evaluated it
+    const double* dspec; const double* noise;               // [F][T] (the chi^2 fit), or null
+    int full, fused;                                        // fullMos (amplitudes) / rotMos; bit 0 of MosaicArgs::fused
+    int nb;                                                 // workgroups per chunk (per pair) of the window sums
+};
+__device__ inline int taper_of(int k, int n) { return 2 * (k > 0 ? 1 : 0) + (k < n - 1 ? 1 : 0); }
+// chunk k's term at its element (r, c): ((A * chunk) * mask) * exp(1j * phi)   [rotMos: (chunk * mask) * exp(1j * rot)]
+__device__ inline cplx fit_term(const FitArgs& a, int k, int rv, int cv, int r, int c) {
+    const cplx v = a.chunks[((int64_t)k * a.cwf + r) * a.cwt + c];
+    const double m = a.rows[rv * a.cwf + r] * a.cols[cv * a.cwt + c];
+    const double* q = a.coef + 3 * (int64_t)k;
+    const cplx s = a.full ? mk(q[0] * v.x, q[0] * v.y) : v;
+    return cmul_np(mk(s.x * m, s.y * m), mk(q[1], q[2]), (a.fused & 1) != 0);
+}
+// chunk k's tapered, rotated element WITHOUT its amplitude (the y of rotDer / fullMosGrad / fullMosHess), by plain products
+__device__ inline cplx fit_y(const FitArgs& a, int k, int rv, int cv, int r, int c, bool rotated) {
+    const cplx v = a.chunks[((int64_t)k * a.cwf + r) * a.cwt + c];
+    const double m = a.rows[rv * a.cwf + r] * a.cols[cv * a.cwt + c];
+    const cplx y = mk(v.x * m, v.y * m);
+    const double* q = a.coef + 3 * (int64_t)k;
+    return rotated ? y * mk(q[1], q[2]) : y;
+}
+
+// (1) W[R][C] and, with `partial`, this workgroup's share of -sum |W|^2 (sign applied at the end) or nansum(((|W|^2 - dspec) / N)^2)
+__global__ void __launch_bounds__(256) fit_gather_kernel(FitArgs a, cplx* __restrict__ W, double* __restrict__ partial) {
+    __shared__ double red[4];
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double term = 0.0;
+    if (q < a.F * a.T) {
+        const int R = (int)(q / a.T), C = (int)(q - (int64_t)R * a.T);
+        int cf0 = 0, cf1 = 0, ct0 = 0, ct1 = 0;
+        if (a.ncf > 1) { const int k = R / a.hf; cf0 = max(k - 1, 0); cf1 = min(k, a.ncf - 1); }
+        if (a.nct > 1) { const int k = C / a.ht; ct0 = max(k - 1, 0); ct1 = min(k, a.nct - 1); }
+        double ox = 0.0, oy = 0.0;                              // E_recov starts as zeros and receives `+=` in loop order
+        for (int cf = cf0; cf <= cf1; ++cf)
+            for (int ct = ct0; ct <= ct1; ++ct) {
+                const cplx y = fit_term(a, cf * a.nct + ct, taper_of(cf, a.ncf), taper_of(ct, a.nct), R - cf * a.hf, C - ct * a.ht);
+                ox = ox + y.x; oy = oy + y.y;
+            }
+        W[q] = mk(ox, oy);
+        const double M = ox * ox + oy * oy;
+        if (a.dspec) {
+            const double t = (M - a.dspec[q]) / a.noise[q];
+            term = t * t;
+            if (term != term) term = 0.0;                       // nansum
+        } else {
+            term = M;
+        }
+    }
+    if (partial) {                                              // (the same for every thread of the launch)
+        const double s = block_sum(term, red);
+        if (threadIdx.x == 0) partial[blockIdx.x] = s;
+    }
+}
+
+// (2) blockIdx.x = chunk, blockIdx.y = its share of the window.  rot: sum 2 Im(conj(E - y e^{i phi}) y e^{i phi}) (ththmod.py:1913-1918);
+// full: nansum(4 (M - dspec) y e^{i phi} conj(W) / N^2) (ththmod.py:2085-2098), both parts.  part[chunk][share][2]
+__global__ void __launch_bounds__(256) fit_grad_kernel(FitArgs a, const cplx* __restrict__ W, double* __restrict__ part) {
+    __shared__ double red[4];
+    const int k = (int)blockIdx.x, cf = k / a.nct, ct = k - cf * a.nct;
+    const int rv = taper_of(cf, a.ncf), cv = taper_of(ct, a.nct);
+    const int64_t w0 = (int64_t)cf * a.hf * a.T + (int64_t)ct * a.ht;
+    const cplx ph = mk(a.coef[3 * (int64_t)k + 1], a.coef[3 * (int64_t)k + 2]);
+    const int n = a.cwf * a.cwt;
+    double s0 = 0.0, s1 = 0.0;
+    for (int e = (int)(blockIdx.y * 256 + threadIdx.x); e < n; e += a.nb * 256) {
+        const int r = e / a.cwt, c = e - r * a.cwt;
+        const int64_t pix = w0 + (int64_t)r * a.T + c;
+        const cplx y = fit_y(a, k, rv, cv, r, c, false), Wv = W[pix];
+        if (!a.full) {
+            // (y e^{i rot} as the gather formed it: where the chunk is alone in a pixel the difference is exactly zero, as on the host)
+            const cplx xx = Wv - cmul_np(y, ph, (a.fused & 1) != 0);
+            const cplx t = (conj(xx) * y) * ph;
+            s0 = s0 + 2 * t.y;
+        } else {
+            const double wgt = 4 * ((Wv.x * Wv.x + Wv.y * Wv.y) - a.dspec[pix]);
+            const double ns = a.noise[pix], n2 = ns * ns;
+            const cplx t = (mk(wgt * y.x, wgt * y.y) * ph) * conj(Wv);
+            const double tx = t.x / n2, ty = t.y / n2;
+            if (tx == tx && ty == ty) { s0 = s0 + tx; s1 = s1 + ty; }     // nansum of a complex array: an element is NaN if either part is
+        }
+    }
+    s0 = block_sum(s0, red);
+    s1 = block_sum(s1, red);
+    if (threadIdx.x == 0) {
+        double* o = part + ((int64_t)k * a.nb + blockIdx.y) * 2;
+        o[0] = s0; o[1] = s1;
+    }
+}
+
+// (3) workgroup 0: the objective from the gather's partials; the others: one thread per chunk adds its shares in order.
+// out[0] = value, out[1 + k] = d/d phi_k, out[1 + n + k] = d/d A_k (full only)
+__global__ void __launch_bounds__(1024) fit_finish_kernel(FitArgs a, const double* __restrict__ partial, int64_t npartial,
+                                                          const double* __restrict__ part, int want_grad, double* __restrict__ out) {
+    __shared__ double red[16];
+    const int n = a.ncf * a.nct;
+    if (blockIdx.x == 0) {
+        double s = 0.0;
+        for (int64_t i = threadIdx.x; i < npartial; i += 1024) s = s + partial[i];
+        s = block_sum(s, red);
+        if (threadIdx.x == 0) out[0] = a.full ? s : -s;
+        return;
+    }
+    const int64_t k = (int64_t)(blockIdx.x - 1) * 1024 + threadIdx.x;
+    if (!want_grad || k >= n) return;
+    double s0 = 0.0, s1 = 0.0;
+    for (int b = 0; b < a.nb; ++b) { s0 = s0 + part[(k * a.nb + b) * 2]; s1 = s1 + part[(k * a.nb + b) * 2 + 1]; }
+    if (a.full) {                                               // temp = conj(sum): A * temp.imag, temp.real
+        out[1 + k] = a.coef[3 * k] * (-s1);
+        out[1 + n + k] = s0;
+    } else {
+        out[1 + k] = s0;
+        out[1 + n + k] = 0.0;
+    }
+}
+
+// ---- fullMosHess (ththmod.py:2105-2310).  Job j = 9 N + 3 (dt + 1) + (df + 1): chunk N and its neighbour M = N + (df, dt); the three
+// sums over the overlap of their windows.  blockIdx.x = job, blockIdx.y = share; part[job][share][3] = dAndAm, dAndpm, dpndpm
+struct HessJob { int N, M, valid; };
+__device__ inline HessJob hess_job(const FitArgs& a, int64_t j, int& df, int& dt) {
+    HessJob h;
+    h.N = (int)(j / 9);
+    const int d = (int)(j - 9 * (int64_t)h.N);
+    dt = d / 3 - 1; df = d - 3 * (d / 3) - 1;
+    const int cfN = h.N / a.nct, ctN = h.N - cfN * a.nct, cfM = cfN + df, ctM = ctN + dt;
+    h.valid = (cfM >= 0 && cfM < a.ncf && ctM >= 0 && ctM < a.nct) ? 1 : 0;
+    h.M = cfM * a.nct + ctM;
+    return h;
+}
+__global__ void __launch_bounds__(256) fit_hess_kernel(FitArgs a, const cplx* __restrict__ W, double* __restrict__ part) {
+    __shared__ double red[4];
+    int df, dt;
+    const HessJob h = hess_job(a, (int64_t)blockIdx.x, df, dt);
+    if (!h.valid) return;                                       // (the whole workgroup)
+    const int cfN = h.N / a.nct, ctN = h.N - cfN * a.nct, cfM = cfN + df, ctM = ctN + dt;
+    const int nr = df == 0 ? a.cwf : a.hf, nc = dt == 0 ? a.cwt : a.ht;           // the overlap (ththmod.py:2183-2210)
+    const int rN0 = df == 1 ? a.hf : 0, rM0 = df == -1 ? a.hf : 0, cN0 = dt == 1 ? a.ht : 0, cM0 = dt == -1 ? a.ht : 0;
+    const int rvN = taper_of(cfN, a.ncf), cvN = taper_of(ctN, a.nct), rvM = taper_of(cfM, a.ncf), cvM = taper_of(ctM, a.nct);
+    const double AN = a.coef[3 * (int64_t)h.N], AM = a.coef[3 * (int64_t)h.M];
+    const bool same = h.M == h.N;
+    const int64_t w0 = ((int64_t)cfN * a.hf + rN0) * a.T + (int64_t)ctN * a.ht + cN0;
+    const int n = nr * nc;
+    double sAA = 0.0, sAp = 0.0, spp = 0.0;
+    for (int e = (int)(blockIdx.y * 256 + threadIdx.x); e < n; e += a.nb * 256) {
+        const int r = e / nc, c = e - r * nc;
+        const int64_t pix = w0 + (int64_t)r * a.T + c;
+        const cplx yN = fit_y(a, h.N, rvN, cvN, rN0 + r, cN0 + c, true), yM = fit_y(a, h.M, rvM, cvM, rM0 + r, cM0 + c, true);
+        const cplx Wv = W[pix], Ws = conj(Wv);
+        const cplx tN = yN * Ws, tM = yM * Ws, cc = conj(yM) * yN;
+        const double wt = (Wv.x * Wv.x + Wv.y * Wv.y) - a.dspec[pix];
+        const double ns = a.noise[pix], n2 = ns * ns;
+        double vAA = 8 * tM.x * tN.x + 4 * wt * cc.x;
+        double vAp = -8 * AM * tM.y * tN.x + 4 * wt * AM * cc.y;
+        double vpp = 8 * AN * AM * tM.y * tN.y + 4 * AN * AM * wt * cc.x;
+        if (same) { vAp = vAp - 4 * wt * tN.y; vpp = vpp - 4 * AN * wt * tN.x; }
+        sAA = sAA + vAA / n2; sAp = sAp + vAp / n2; spp = spp + vpp / n2;       // numpy.sum: a NaN or an infinity stays
+    }
+    sAA = block_sum(sAA, red);
+    sAp = block_sum(sAp, red);
+    spp = block_sum(spp, red);
+    if (threadIdx.x == 0) {
+        double* o = part + ((int64_t)blockIdx.x * a.nb + blockIdx.y) * 3;
+        o[0] = sAA; o[1] = sAp; o[2] = spp;
+    }
+}
+// One thread per job adds its shares in order and writes the entries.  The reference writes H[A_N, A_M] and H[p_N, p_M] from both
+// visits (N, M) and (M, N), the later one (the larger N: it is the outer loop) last -- that value is kept, on both sides of the diagonal.
+__global__ void __launch_bounds__(256) fit_hess_finish_kernel(FitArgs a, const double* __restrict__ part, double* __restrict__ H) {
+    const int n = a.ncf * a.nct;
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x, P = 2 * (int64_t)n - 1;
+    if (j >= 9 * (int64_t)n) return;
+    int df, dt;
+    const HessJob h = hess_job(a, j, df, dt);
+    if (!h.valid) return;
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int b = 0; b < a.nb; ++b)
+        for (int q = 0; q < 3; ++q) s[q] = s[q] + part[(j * a.nb + b) * 3 + q];
+    const int64_t pN = h.N - 1, pM = h.M - 1, AN = h.N + n - 1, AM = h.M + n - 1;
+    if (h.N >= h.M) { H[AN * P + AM] = s[0]; H[AM * P + AN] = s[0]; }
+    if (h.M > 0) {
+        H[AN * P + pM] = s[1]; H[pM * P + AN] = s[1];
+        if (h.N > 0 && h.N >= h.M) { H[pM * P + pN] = s[2]; H[pN * P + pM] = s[2]; }
+    }
+}
+
+// workgroups per window sum: about four elements a thread, at most 32 (a fixed function of the shape: the sums' order is fixed)
+static int fit_blocks(int64_t cwf, int64_t cwt) { return (int)std::min<int64_t>(std::max<int64_t>(ceil_div(cwf * cwt, 1024), 1), 32); }
+static bool fit_shape_ok(int64_t ncf, int64_t nct, int64_t cwf, int64_t cwt) {
+    return ncf >= 1 && nct >= 1 && cwf >= 1 && cwt >= 1 && ncf * nct < (int64_t(1) << 24) && cwf * cwt < (int64_t(1) << 30) &&
+           (ncf == 1 || cwf % 2 == 0) && (nct == 1 || cwt % 2 == 0);
+}
+static FitArgs fit_args(const scint_c128* chunks, int64_t ncf, int64_t nct, int64_t cwf, int64_t cwt, const double* rows, const double* cols,
+                        const double* coef, int32_t full, int32_t fused, const double* dspec, const double* noise) {
+    FitArgs a{};
+    a.chunks = (const cplx*)chunks; a.ncf = (int)ncf; a.nct = (int)nct; a.cwf = (int)cwf; a.cwt = (int)cwt;
+    a.hf = (int)(cwf / 2); a.ht = (int)(cwt / 2);
+    a.F = (ncf - 1) * (cwf / 2) + cwf; a.T = (nct - 1) * (cwt / 2) + cwt;
+    a.rows = rows; a.cols = cols; a.coef = coef; a.dspec = dspec; a.noise = noise; a.full = full ? 1 : 0; a.fused = fused;
+    a.nb = fit_blocks(cwf, cwt);
+    return a;
+}
+}  // namespace scint
+
+extern "C" int32_t scint_mosaic_fit_workspace_bytes(int64_t ncf, int64_t nct, int64_t cwf, int64_t cwt, size_t* bytes) {
+    SCINT_REQUIRE(bytes != nullptr, "mosaic_fit_workspace_bytes: null output");
+    SCINT_REQUIRE(fit_shape_ok(ncf, nct, cwf, cwt), "mosaic_fit_workspace_bytes: bad shape (sizes are even along an axis of several chunks)");
+    const int64_t n = ncf * nct, F = (ncf - 1) * (cwf / 2) + cwf, T = (nct - 1) * (cwt / 2) + cwt, nb = fit_blocks(cwf, cwt);
+    *bytes = align_up(sizeof(double) * (size_t)ceil_div(F * T, 256), 256) + align_up(sizeof(double) * (size_t)(9 * n * nb * 3), 256) + 256;
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_mosaic_fit_eval(const scint_c128* chunks, int64_t ncf, int64_t nct, int64_t cwf, int64_t cwt, const double* rows,
+                                         const double* cols, const double* coef, int32_t full, int32_t numpy_fused, const double* dspec,
+                                         const double* noise, scint_c128* W, int32_t want, double* out, void* workspace,
+                                         size_t workspace_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    SCINT_REQUIRE(chunks && rows && cols && coef && W, "mosaic_fit_eval: null pointer");
+    SCINT_REQUIRE(fit_shape_ok(ncf, nct, cwf, cwt), "mosaic_fit_eval: bad shape (sizes are even along an axis of several chunks)");
+    SCINT_REQUIRE(want >= 0 && want <= 2, "mosaic_fit_eval: want is 0 (the mosaic), 1 (+ objective) or 2 (+ gradient)");
+    SCINT_REQUIRE(want == 0 || (out && workspace), "mosaic_fit_eval: null output or workspace");
+    SCINT_REQUIRE(want == 0 || !full || (dspec && noise), "mosaic_fit_eval: the chi^2 fit needs the dynamic spectrum and its noise");
+    // (the plain fullMos, and rotFit, do not read the dynamic spectrum)
+    const FitArgs a = fit_args(chunks, ncf, nct, cwf, cwt, rows, cols, coef, full, numpy_fused, (want && full) ? dspec : nullptr,
+                               (want && full) ? noise : nullptr);
+    const int64_t n = ncf * nct, nblk = ceil_div(a.F * a.T, 256);
+    SCINT_REQUIRE(nblk < (int64_t(1) << 31), "mosaic_fit_eval: mosaic too large");
+    double* partial = nullptr;
+    double* part = nullptr;
+    if (want) {
+        size_t need = 0;
+        if (scint_mosaic_fit_workspace_bytes(ncf, nct, cwf, cwt, &need) != SCINT_OK) return SCINT_E_ARG;
+        if (workspace_bytes < need) { set_error("scint: mosaic_fit workspace too small"); return SCINT_E_WORKSPACE; }
+        partial = (double*)workspace;
+        part = (double*)((char*)workspace + align_up(sizeof(double) * (size_t)nblk, 256));
+    }
+    hipLaunchKernelGGL(fit_gather_kernel, dim3((unsigned)nblk), dim3(256), 0, stream, a, (cplx*)W, partial);
+    if (want >= 2) hipLaunchKernelGGL(fit_grad_kernel, dim3((unsigned)n, (unsigned)a.nb), dim3(256), 0, stream, a, (const cplx*)W, part);
+    if (want) hipLaunchKernelGGL(fit_finish_kernel, dim3((unsigned)(1 + ceil_div(n, 1024))), dim3(1024), 0, stream, a, (const double*)partial, nblk,
+                                 (const double*)part, want >= 2 ? 1 : 0, out);
+    SCINT_LAUNCH_CHECK();
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_mosaic_fit_hess(const scint_c128* chunks, int64_t ncf, int64_t nct, int64_t cwf, int64_t cwt, const double* rows,
+                                         const double* cols, const double* coef, const double* dspec, const double* noise,
+                                         const scint_c128* W, double* H, void* workspace, size_t workspace_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    SCINT_REQUIRE(chunks && rows && cols && coef && dspec && noise && W && H && workspace, "mosaic_fit_hess: null pointer");
+    SCINT_REQUIRE(fit_shape_ok(ncf, nct, cwf, cwt), "mosaic_fit_hess: bad shape (sizes are even along an axis of several chunks)");
+    size_t need = 0;
+    if (scint_mosaic_fit_workspace_bytes(ncf, nct, cwf, cwt, &need) != SCINT_OK) return SCINT_E_ARG;
+    if (workspace_bytes < need) { set_error("scint: mosaic_fit workspace too small"); return SCINT_E_WORKSPACE; }
+    const FitArgs a = fit_args(chunks, ncf, nct, cwf, cwt, rows, cols, coef, 1, 0, dspec, noise);
+    const int64_t n = ncf * nct, P = 2 * n - 1, nblk = ceil_div(a.F * a.T, 256);
+    double* part = (double*)((char*)workspace + align_up(sizeof(double) * (size_t)nblk, 256));
+    SCINT_HIP(hipMemsetAsync(H, 0, sizeof(double) * (size_t)(P * P), stream));
+    hipLaunchKernelGGL(fit_hess_kernel, dim3((unsigned)(9 * n), (unsigned)a.nb), dim3(256), 0, stream, a, (const cplx*)W, part);
+    hipLaunchKernelGGL(fit_hess_finish_kernel, dim3((unsigned)ceil_div(9 * n, 256)), dim3(256), 0, stream, a, (const double*)part, H);
+    SCINT_LAUNCH_CHECK();
+    return SCINT_OK;
+}

@@ -614,6 +614,32 @@ class Dynspec:
         if gs:
             self.gerchberg_saxton(verbose=verbose, pool=pool, niter=niter)
 
+    def refine_wavefield(self, mode="rot", N=None, verbose=False, pool=None, **kw):
+        """Mosaic the chunks with every chunk's phase fitted jointly (``mode="rot"``: ``rotInit`` + ``rotFit``, the reference
+        tutorial's wavefield) or phase and amplitude against the dynamic spectrum (``"full"``: ``fullMosFit``), on the chunks
+        parked in HBM (``ththmod.fit_mosaic``; ``kw`` goes there: x0, method, options).  ``N``: the noise map of ``"full"``
+        (array like ``dyn``, or a number).  Its default is one number for the whole map, ``nanstd(diff(dyn, axis=1)) / sqrt(2)``:
+        that ASSUMES white noise and a spectrum that is smooth in time over one sample (scintillation structure between
+        neighbouring sub-integrations counts as noise otherwise) -- pass a measured map where that does not hold.  ``dyn`` and
+        ``N`` are cropped to the mosaic's extent, as ``fullMosFit`` does.
+        Fills ``self.wavefield`` and ``self.mosaic_params`` (and ``self.mosaic_result``, SciPy's report)."""
+        cls = type(self)
+        if not cls.chunks.present(self):
+            self.thetatheta_chunks(verbose=verbose, pool=pool)
+        chunks_t = cls.chunks.tensor(self, torch.complex128)
+        if mode == "full":
+            dyn = np.asarray(self.dyn, dtype=float)
+            if N is None:
+                N = np.nanstd(np.diff(dyn, axis=1)) / np.sqrt(2.0)
+            ncf, nct, cwf, cwt = (int(v) for v in chunks_t.shape)
+            F, T = (ncf - 1) * (cwf // 2) + cwf, (nct - 1) * (cwt // 2) + cwt      # the gradient wants the mosaic's own extent
+            stack = thth.MosaicStack(chunks_t, dyn[:F, :T], np.broadcast_to(np.asarray(N, dtype=float), dyn.shape)[:F, :T])
+        else:
+            stack = thth.MosaicStack(chunks_t)
+        wf_t, params, res = thth.fit_mosaic(stack, mode=mode, out_device=True, **kw)
+        cls.wavefield.park(self, wf_t)
+        self.mosaic_params, self.mosaic_result = params, res
+
     def gerchberg_saxton(self, niter=1, verbose=False, pool=None):
         """Gerchberg-Saxton: enforce the measured amplitudes and causality (tau >= 0)
         (dynspec.py:1858-1875); the FFT <-> projection iterations run on the GPU."""

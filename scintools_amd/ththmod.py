@@ -24,6 +24,11 @@ sv_sweep_multi     (fit_thetatheta thin)  scint_sv_sweep_multi
 VLBI_chunk_retrieval ththmod.py:1223-1387 scint_cs_batch + scint_cs_complex_batch +
                                           scint_vlbi_composite + scint_eigh_top_batch +
                                           scint_retrieval_tail
+rotMos / fullMos   ththmod.py:1708-1987   scint_mosaic_fit_eval
+rotFit + rotDer,   ththmod.py:1773-2102   scint_mosaic_fit_eval (value and gradient
+fullMosFit + Grad                         from one evaluation: MosaicStack)
+fullMosHess        ththmod.py:2105-2310   scint_mosaic_fit_hess
+rotInit            ththmod.py:1791-1856   scint_mosaic_phase + scint_mosaic_add
 =================  =====================  ========================================
 
 ``tau, fd, eta, edges`` may be bare numbers (us, mHz, s**3, mHz) or, when astropy
@@ -41,7 +46,7 @@ import warnings
 
 import numpy as np
 import torch
-from scipy.optimize import curve_fit
+from scipy.optimize import curve_fit, minimize
 
 from . import _lib, units
 from . import device as _dv
@@ -1552,7 +1557,7 @@ def _mosaic_tapers(ncf, nct, cwf, cwt):
     return variants(cwf, ncf), variants(cwt, nct)
 
 
-def mosaic_device(chunks_t):
+def mosaic_device(chunks_t, angles=None):
     """:func:`mosaic` with the chunks and the wavefield in HBM (device tensor [ncf, nct, cwf, cwt] complex128 -> device tensor
     [F, T]).  The reference's loop (ththmod.py:1548-1553) is sequential, but chunk (cf, ct) only meets its four predecessors
     (cf, ct-1) and (cf-1, ct-1 .. ct+1): chunks with equal 2 cf + ct are independent, their windows disjoint, and every
@@ -1560,7 +1565,8 @@ def mosaic_device(chunks_t):
     observation).  Per step one kernel forms ``(chunk_old * conj(chunk_new) * mask)`` and its sum in NumPy's own summation order
     for every chunk of the step, the sums (16 bytes each) come to the host where ``mean``, ``numpy.angle`` and ``numpy.exp``
     are NumPy's, and a second kernel adds ``chunk_new * mask * exp(1j * rot)``.  Bit-identical to the host loop on the same
-    chunks (tests); the host loop spent 0.26 s on those 961 chunks and needed them on the host (1 GB)."""
+    chunks (tests); the host loop spent 0.26 s on those 961 chunks and needed them on the host (1 GB).
+    ``angles``: a float array [ncf * nct] that receives every chunk's rotation (the reference's ``rotInit`` is this very loop)."""
     lib = _lib.load()
     ncf, nct, cwf, cwt = (int(v) for v in chunks_t.shape)
     rows, cols = _mosaic_tapers(ncf, nct, cwf, cwt)             # (raises for an odd size along an axis of several chunks)
@@ -1603,11 +1609,240 @@ def mosaic_device(chunks_t):
         for k in range(n):
             tot = np.complex128(complex(sums[k, 0], sums[k, 1]))
             mean = tot.dtype.type(tot / count)                       # numpy's _mean: umr_sum(...) / rcount
-            e = np.exp(1j * np.angle(mean))
+            rot = np.angle(mean)
+            e = np.exp(1j * rot)
             ph[k, 0], ph[k, 1] = e.real, e.imag
+            if angles is not None:
+                angles[table[first + k][1]] = rot
         _lib.check(lib.scint_mosaic_add(ptr(E_t), T, ptr(chunks_c), cwf, cwt, jp, n, ptr(rows_t), ptr(cols_t), fused,
                                         ph.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), st), "scint_mosaic_add")
     return E_t
+
+
+# ----------------------------------------------------------------------------
+# the fitted mosaics (ththmod.py:1708-2310): every chunk's phase -- and amplitude -- a free parameter
+# ----------------------------------------------------------------------------
+class MosaicStack:
+    """The chunk stack of a mosaic, its tapers and (optionally) the dynamic spectrum and its noise map, in HBM: what an
+    optimiser of ``rotFit`` / ``fullMosFit`` evaluates tens to hundreds of times.  ``chunks``: NumPy array, stripped Quantity or
+    device tensor [ncf, nct, cwf, cwt]; sizes are even along an axis of several chunks (``ValueError`` otherwise, as
+    :func:`mosaic_device`).  One evaluation is three launches (csrc/mosaic.hip): the mosaic as a gather, the per-chunk window
+    sums, their fixed-order totals -- the same inputs give the same bits.
+
+    ``dspec`` / ``N`` keep the reference's shape rules: the objective crops them to the mosaic (``dspec[:F, :T]``), gradient and
+    Hessian need exactly the mosaic's shape and raise ``ValueError`` otherwise, as the NumPy broadcast there does."""
+
+    def __init__(self, chunks, dspec=None, N=None):
+        self._lib = _lib.load()
+        if isinstance(chunks, torch.Tensor):
+            chunks_t = chunks.to(torch.complex128)
+        else:
+            chunks_t = _dv.to_device(np.ascontiguousarray(np.asarray(getattr(chunks, "value", chunks), dtype=complex)), torch.complex128)
+        if chunks_t.dim() != 4:
+            raise ValueError("MosaicStack: chunks are [ncf, nct, cwf, cwt]")
+        self.chunks_t = chunks_t.contiguous()
+        self.ncf, self.nct, self.cwf, self.cwt = (int(v) for v in chunks_t.shape)
+        rows, cols = _mosaic_tapers(self.ncf, self.nct, self.cwf, self.cwt)      # (raises for an odd size on a tapered axis)
+        self.n = self.ncf * self.nct
+        self.shape = ((self.ncf - 1) * (self.cwf // 2) + self.cwf, (self.nct - 1) * (self.cwt // 2) + self.cwt)
+        self._rows_t, self._cols_t = _dv.to_device(rows, torch.float64), _dv.to_device(cols, torch.float64)
+        modes = _numpy_mosaic_modes(self.cwf, self.cwt)
+        if modes is None:
+            warnings.warn("scintools_amd: this NumPy evaluates the mosaic's products in an unknown way; the device mosaic agrees with "
+                          "the reference's host loop to rounding, not bit for bit")
+            modes = (False, False)
+        self._fused = 1 if modes[0] else 0
+        need = ctypes.c_size_t()
+        _lib.check(self._lib.scint_mosaic_fit_workspace_bytes(self.ncf, self.nct, self.cwf, self.cwt, ctypes.byref(need)), "mosaic_fit_workspace_bytes")
+        self._ws_bytes = need.value
+        self._W_t = None
+        self._maps = [self._map(dspec), self._map(N)]
+
+    def with_maps(self, dspec, N):
+        """A stack on the SAME chunks and tapers in HBM with another dynamic spectrum and noise map (and a mosaic buffer of its own)."""
+        return MosaicStack(self.chunks_t, dspec, N)
+
+    def _map(self, arr):
+        """(device crop to the mosaic or None, is exactly the mosaic's shape, host shape)"""
+        if arr is None:
+            return None
+        if isinstance(arr, torch.Tensor):
+            shape = tuple(int(v) for v in arr.shape)
+            crop = arr
+        else:
+            crop = np.asarray(getattr(arr, "value", arr), dtype=float)
+            shape = crop.shape
+        F, T = self.shape
+        if len(shape) != 2 or shape[0] < F or shape[1] < T:
+            return (None, False, shape)
+        crop = crop[:F, :T]
+        crop_t = crop.to(torch.float64).contiguous() if isinstance(crop, torch.Tensor) else _dv.to_device(np.ascontiguousarray(crop), torch.float64)
+        return (crop_t, shape == (F, T), shape)
+
+    def _fit_maps(self, exact):
+        out = []
+        for m, name in zip(self._maps, ("dspec", "N")):
+            if m is None:
+                raise ValueError(f"MosaicStack: the chi^2 fit needs {name}")
+            if m[0] is None or (exact and not m[1]):
+                raise ValueError(f"operands could not be broadcast together with shapes {self.shape} {m[2]} ({name})")
+            out.append(m[0])
+        return out
+
+    # -- parameters -> per-chunk coefficients (amplitude, exp(1j * phase) in NumPy) -------------------------------------------
+    def _coef(self, phases, amps):
+        c = np.empty((self.n, 3))
+        c[:, 0] = 1.0 if amps is None else amps
+        e = np.exp(1j * np.concatenate(([0.0], np.asarray(phases, dtype=float))))       # chunk 0: exp(0j) = 1 + 0j, the same product
+        c[:, 1], c[:, 2] = e.real, e.imag
+        return _dv.to_device(c, torch.float64)
+
+    def _split(self, p):
+        p = np.asarray(p, dtype=float)
+        if p.shape != (2 * self.n - 1,):
+            raise IndexError(f"fullMos: p holds {self.n - 1} phases and {self.n} amplitudes, got shape {p.shape}")
+        return p[:self.n - 1], p[self.n - 1:]
+
+    def _rot_x(self, x):
+        x = np.asarray(x, dtype=float)
+        if x.shape != (self.n - 1,):
+            raise IndexError(f"rotMos: x holds {self.n - 1} phases, got shape {x.shape}")
+        return x
+
+    def _eval(self, coef_t, full, want, maps=(None, None), W_t=None):
+        if W_t is None:
+            if self._W_t is None:
+                self._W_t = empty(self.shape, torch.complex128)
+            W_t = self._W_t
+        out_t = empty((1 + 2 * self.n,), torch.float64) if want else None
+        ws = workspace.get(self._ws_bytes) if want else None
+        _lib.check(self._lib.scint_mosaic_fit_eval(ptr(self.chunks_t), self.ncf, self.nct, self.cwf, self.cwt, ptr(self._rows_t), ptr(self._cols_t),
+                                                   ptr(coef_t), 1 if full else 0, self._fused, ptr(maps[0]) if maps[0] is not None else None,
+                                                   ptr(maps[1]) if maps[1] is not None else None, ptr(W_t), want,
+                                                   ptr(out_t) if want else None, ptr(ws) if want else None, ws.numel() if want else 0,
+                                                   stream_ptr()), "scint_mosaic_fit_eval")
+        return W_t, (out_t.cpu().numpy() if want else None)
+
+    def _mosaic(self, coef_t, full, out_device):
+        W_t, _ = self._eval(coef_t, full, 0, W_t=empty(self.shape, torch.complex128))
+        return W_t if out_device else W_t.cpu().numpy()
+
+    # -- the phase fit ------------------------------------------------------------------------------------------------------------
+    def rot_init(self):
+        """``rotInit``: the greedy mosaic's own angles (the reference's ``rotInit`` and ``mosaic`` are the same loop)."""
+        angles = np.zeros(self.n)
+        mosaic_device(self.chunks_t, angles=angles)
+        return angles[1:]
+
+    def rot_mosaic(self, x, out_device=False):
+        """``rotMos(chunks, x)``: bit-identical to the host loop on the same chunks."""
+        return self._mosaic(self._coef(self._rot_x(x), None), False, out_device)
+
+    def rot_value_and_grad(self, x):
+        """(``rotFit(x, chunks)``, ``rotDer(x, chunks)``) from one evaluation."""
+        _, out = self._eval(self._coef(self._rot_x(x), None), False, 2)
+        return float(out[0]), out[2:1 + self.n].copy()
+
+    def rot_value(self, x):
+        return float(self._eval(self._coef(self._rot_x(x), None), False, 1)[1][0])
+
+    # -- the chi^2 fit ------------------------------------------------------------------------------------------------------------
+    def full_mosaic(self, p, out_device=False):
+        """``fullMos(chunks, p)``: bit-identical to the host loop on the same chunks."""
+        ph, amp = self._split(p)
+        return self._mosaic(self._coef(ph, amp), True, out_device)
+
+    def full_value(self, p):
+        """``fullMosFit``: dspec and N cropped to the mosaic."""
+        ph, amp = self._split(p)
+        return float(self._eval(self._coef(ph, amp), True, 1, self._fit_maps(False))[1][0])
+
+    def full_value_and_grad(self, p):
+        """(``fullMosFit``, ``fullMosGrad``) from one evaluation; dspec and N of exactly the mosaic's shape."""
+        ph, amp = self._split(p)
+        _, out = self._eval(self._coef(ph, amp), True, 2, self._fit_maps(True))
+        return float(out[0]), np.concatenate((out[2:1 + self.n], out[1 + self.n:]))
+
+    def full_hess(self, p):
+        """``fullMosHess``: dense [2 n - 1, 2 n - 1], zero outside the neighbour band, exactly symmetric."""
+        ph, amp = self._split(p)
+        maps = self._fit_maps(True)
+        coef_t = self._coef(ph, amp)
+        W_t, _ = self._eval(coef_t, True, 0)
+        P = 2 * self.n - 1
+        H_t = empty((P, P), torch.float64)
+        ws = workspace.get(self._ws_bytes)
+        _lib.check(self._lib.scint_mosaic_fit_hess(ptr(self.chunks_t), self.ncf, self.nct, self.cwf, self.cwt, ptr(self._rows_t), ptr(self._cols_t),
+                                                   ptr(coef_t), ptr(maps[0]), ptr(maps[1]), ptr(W_t), ptr(H_t), ptr(ws), ws.numel(), stream_ptr()),
+                   "scint_mosaic_fit_hess")
+        return H_t.cpu().numpy()
+
+
+def _as_stack(chunks, dspec=None, N=None):
+    if isinstance(chunks, MosaicStack):
+        return chunks if dspec is None and N is None else chunks.with_maps(dspec, N)
+    return MosaicStack(chunks, dspec, N)
+
+
+def rotMos(chunks, x):
+    """Mosaic with given chunk phases (ththmod.py:1708-1770).  ``chunks`` may be a :class:`MosaicStack`."""
+    return _as_stack(chunks).rot_mosaic(x)
+
+
+def rotFit(x, chunks):
+    """-sum |rotMos(chunks, x)|^2 (ththmod.py:1773-1788)."""
+    return np.float64(_as_stack(chunks).rot_value(x))
+
+
+def rotInit(chunks):
+    """The greedy mosaic's phases as a start for :func:`rotFit` (ththmod.py:1791-1856)."""
+    return _as_stack(chunks).rot_init()
+
+
+def rotDer(x, chunks):
+    """Analytic gradient of :func:`rotFit` (ththmod.py:1859-1919)."""
+    return _as_stack(chunks).rot_value_and_grad(x)[1]
+
+
+def fullMos(chunks, p):
+    """Mosaic with given chunk phases and amplitudes (ththmod.py:1922-1987)."""
+    return _as_stack(chunks).full_mosaic(p)
+
+
+def fullMosFit(p, chunks, dspec, N):
+    """chi^2 of |fullMos|^2 against the dynamic spectrum (ththmod.py:1990-2016)."""
+    return np.float64(_as_stack(chunks, dspec, N).full_value(p))
+
+
+def fullMosGrad(p, chunks, dspec, N):
+    """Analytic gradient of :func:`fullMosFit` (ththmod.py:2019-2102)."""
+    return _as_stack(chunks, dspec, N).full_value_and_grad(p)[1]
+
+
+def fullMosHess(p, chunks, dspec, N):
+    """Analytic Hessian of :func:`fullMosFit` (ththmod.py:2105-2310)."""
+    return _as_stack(chunks, dspec, N).full_hess(p)
+
+
+def fit_mosaic(stack, mode="rot", x0=None, method=None, options=None, out_device=False):
+    """Fit every chunk's phase (``mode="rot"``: maximise the coherent power, L-BFGS-B) or phase and amplitude (``"full"``:
+    minimise chi^2 against the stack's dynamic spectrum, Newton-CG with the analytic Hessian) with ``scipy.optimize.minimize``
+    on the device objective and derivatives.  The start is ``rot_init()`` (amplitudes 1).  Returns (wavefield, parameters,
+    OptimizeResult); the wavefield stays on the device with ``out_device``."""
+    if mode not in ("rot", "full"):
+        raise ValueError("fit_mosaic: mode is 'rot' or 'full'")
+    if not isinstance(stack, MosaicStack):
+        stack = MosaicStack(stack)
+    if x0 is None:
+        x0 = stack.rot_init()
+        if mode == "full":
+            x0 = np.concatenate((x0, np.ones(stack.n)))
+    x0 = np.asarray(x0, dtype=float)
+    if mode == "rot":
+        res = minimize(stack.rot_value_and_grad, x0, jac=True, method=method or "L-BFGS-B", options=options)
+        return stack.rot_mosaic(res.x, out_device=out_device), res.x, res
+    res = minimize(stack.full_value_and_grad, x0, jac=True, hess=stack.full_hess, method=method or "Newton-CG", options=options)
+    return stack.full_mosaic(res.x, out_device=out_device), res.x, res
 
 
 def chunk_cut_device(dyn_t, origins, cwf, cwt, fortran_order=False):
