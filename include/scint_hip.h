@@ -552,6 +552,37 @@ int32_t scint_fft2_workspace_bytes(int64_t rows, int64_t cols, size_t* bytes /*H
 int32_t scint_fft2(const scint_c128* in, scint_c128* out, int64_t rows, int64_t cols,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- split-step screen simulator: scint_sim.Simulation (scint_sim.py:23-311, Coles et al. 2010) -------------------
+ * x (nx) is the strided axis of every array here, y (ny) the contiguous one.  Sizes: nx a power of two in [16, 2^17]
+ * (the column passes of the FFT, at most 65535 butterflies each), ny a power of two in [16, 8192] (the row kernel), nx * ny <= 2^28.
+ * scint_sim_screen: w[nx][ny], the weights of get_screen / swdsp from the index alone (the reference's fill order, its
+ *   off-by-one on the ky = 0 line and the entries it leaves at zero included), and xyp = real(fft2(w (z1 + i z2))) for
+ *   the two normal draws z1, z2[nx][ny].  a, b, c: the anisotropy coefficients of swdsp; con = sqrt(consp);
+ *   alf = -(alpha + 2) / 4; inner2 = inner^2.
+ * scint_sim_field: spe[:, f0:f1] (complex64 [nx][nf]) and spi = |spe|^2 (float32 [nx][nf], rounded as the reference's
+ *   complex64 product) of E_f = ifft2(frfilt3(fft2(exp(i xyp scale[f])))), column ny/2, for the frequencies f0 <= f < f1;
+ *   scale[nf] is a DEVICE array.  The frequencies go in groups of as many as the workspace holds
+ *   (scint_sim_field_workspace_bytes(nx, ny, group)); the result does not depend on the grouping while a group's planes
+ *   (16 nx ny bytes per frequency) stay below the 300 MiB at which the column transform changes from radix passes to its
+ *   tiled form -- a larger group agrees to rounding, not bit for bit.  With xyi != NULL
+ *   and f1 == nf the intensity |E|^2 [nx][ny] of the last frequency is written too.  Only column ny/2 of every inverse
+ *   transform is computed (a row reduction and one 1-D inverse transform per frequency); SCINT_SIM_COLUMN=0
+ *   (environment, read per call) takes the full inverse 2-D transform of every frequency and picks the column.
+ * scint_sim_last_route: of the LAST scint_sim_field of the process -- column = 1 if it took the shortcut, groups = the
+ *   groups it ran (tests).
+ * scint_sim_pulse: get_pulse's pulsewin before its transpose, out[nx][2 nf] = roll(|fft(spe * window, 2 nf)|^2, nf)
+ *   (the roll of the flattened array, as np.roll without an axis); 2 nf a power of two in [16, 8192]. */
+int32_t scint_sim_screen_workspace_bytes(int64_t nx, int64_t ny, size_t* bytes /*HOST*/);
+int32_t scint_sim_screen(const double* z1, const double* z2, int64_t nx, int64_t ny, double dqx, double dqy,
+                         double a, double b, double c, double con, double alf, double inner2, double* w,
+                         double* xyp, void* workspace, size_t workspace_bytes, void* stream);
+int32_t scint_sim_field_workspace_bytes(int64_t nx, int64_t ny, int64_t group, size_t* bytes /*HOST*/);
+int32_t scint_sim_field(const double* xyp, int64_t nx, int64_t ny, const double* scale, int64_t nf, int64_t f0,
+                        int64_t f1, double ffconx, double ffcony, void* spe, float* spi, double* xyi,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int32_t scint_sim_last_route(int32_t* column /*HOST*/, int64_t* groups /*HOST*/);
+int32_t scint_sim_pulse(const void* spe, int64_t nx, int64_t nf, const double* window, double* out, void* stream);
+
 /* ---- thin-screen curvature search: two_curve_map + singularvalue_calc (ththmod.py:496-513, 1557-1636) ----------------
  * The 'thin' fitting procedure of Dynspec.prep_thetatheta (dynspec.py:1480-1516) models only the region near the arclet apexes:
  * a RECTANGULAR theta-theta map thth[theta2, theta1] (rows: the arclet centres th2[M2], columns: the main-arc centres th1[M1],

@@ -129,6 +129,13 @@ _SIGNATURES = {
                               POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double), c_int64,
                               c_double, c_int32, c_int64, _P, _P, _P, _P, c_size_t, _P], c_int32),
     "scint_fft2": ([_P, _P, c_int64, c_int64, _P, c_size_t, _P], c_int32),
+    "scint_sim_screen_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
+    "scint_sim_screen": ([_P, _P, c_int64, c_int64, c_double, c_double, c_double, c_double, c_double, c_double, c_double, c_double,
+                          _P, _P, _P, c_size_t, _P], c_int32),
+    "scint_sim_field_workspace_bytes": ([c_int64, c_int64, c_int64, POINTER(c_size_t)], c_int32),
+    "scint_sim_field": ([_P, c_int64, c_int64, _P, c_int64, c_int64, c_int64, c_double, c_double, _P, _P, _P, _P, c_size_t, _P], c_int32),
+    "scint_sim_last_route": ([POINTER(c_int32), POINTER(c_int64)], c_int32),
+    "scint_sim_pulse": ([_P, c_int64, c_int64, _P, _P, _P], c_int32),
 }
 
 _lib = None

@@ -4,6 +4,7 @@
 //   scint_cs                conjugate spectrum of a chunk (ththmod.py:777-787)
 //   scint_model_from_recov  ifft2(ifftshift(recov)).real  (ththmod.py:322-324), complex-to-real
 //   scint_mean / scint_chisq  small deterministic reductions
+//   scint_sim_*             the split-step screen simulator (scint_sim.py), functors in sim.hpp
 //
 // Every transform is "source -> row FFT -> column FFT -> sink":
 //   RowSource  produces element (row, j) of the padded real/complex input (this is where
@@ -32,6 +33,7 @@
 #include "fft.hpp"
 #include "packed.hpp"
 #include "prof.hpp"
+#include "sim.hpp"
 #include "sspec.hpp"
 
 namespace scint {
@@ -1857,4 +1859,142 @@ extern "C" int32_t scint_chisq_sweep(const scint_c128* cs, const scint_cs_geom* 
     if (!again.empty()) SCINT_HIP(hipStreamSynchronize(st));
     g_chisq_redone = (int64_t)again.size();
     return SCINT_OK;
+}
+
+// ------------------------------------------------------------------------------
+// scint_sim_screen / scint_sim_field / scint_sim_pulse: the split-step simulator (functors: sim.hpp)
+// ------------------------------------------------------------------------------
+namespace scint {
+static int32_t g_sim_column = 1;
+static int64_t g_sim_groups = 0;
+
+static int32_t sim_check_shape(int64_t nx, int64_t ny) {
+    // x is the strided axis (run_cols_fft: EVERY radix pass puts len / radix butterflies in grid.y, at most 65535; make_col_plan ends
+    // 2^17 with a radix-32 pass (4096) but 2^18 with a radix-4 one (65536)), y the contiguous one (launch_fft_rows)
+    SCINT_REQUIRE(is_pow2(nx) && nx >= 16 && nx <= (1 << 17), "sim: nx must be a power of two in [16, 131072]");
+    SCINT_REQUIRE(is_pow2(ny) && ny >= 16 && ny <= 8192, "sim: ny must be a power of two in [16, 8192]");
+    SCINT_REQUIRE(nx * ny <= ((int64_t)1 << 28), "sim: nx * ny must not exceed 2^28");
+    return SCINT_OK;
+}
+// frequencies per group: two [nx][ny] complex planes each (the column passes' working array and their natural-order result) and one column of g
+static size_t sim_freq_bytes(int64_t nx, int64_t ny) { return sizeof(cplx) * (size_t)(2 * nx * ny + nx); }
+static int64_t sim_group_max(int64_t nx) { return std::min<int64_t>(4096, ((int64_t)1 << 28) / nx); }
+
+// E = ifft2(frfilt3(fft2(exp(i xyp scale)))) of `cnt` frequencies by the full inverse transform: column ny/2 -> spe (if given), the plane
+// of frequency nf - 1 -> xyi (if given)
+static int32_t sim_full(const double* xyp, const double* scale, int64_t nx, int64_t ny, int64_t nf, int64_t f, int64_t cnt,
+                        double ffconx, double ffcony, float* spe, float* spi, double* xyi, cplx* A, cplx* B, hipStream_t stream) {
+    const int64_t plane = nx * ny;
+    ArrayLoad a_ld{A, (int)ny, plane};
+    ArrayStore a_st{A, (int)ny, plane};
+    ArrayLoad b_ld{B, (int)ny, plane};
+    ArrayStore b_st{B, (int)ny, plane};
+    int32_t rc = run_cols_fft(nx, ny, cnt, SimPhaseLoad{xyp, scale + f, (int)ny}, a_ld, a_st, b_st, stream);
+    if (rc != SCINT_OK) return rc;
+    const SimFilter filt{scale + f, ffconx, ffcony, (int)nx, (int)ny, ilog2(nx), cnt * nx};
+    rc = launch_fft_rows(ny, cnt * nx, SimRowLoad{B, (int)ny}, SimFilterStore{filt, B}, stream);
+    if (rc != SCINT_OK) return rc;
+    rc = launch_fft_rows(ny, cnt * nx, SimRowLoad{B, (int)ny}, SimRowStore{B, (int)ny}, stream);
+    if (rc != SCINT_OK) return rc;
+    return run_cols_fft(nx, ny, cnt, b_ld, b_ld, b_st,
+                        SimFullStore{spe, spi, xyi, (int)nf, (int)ny, (int)f, 1.0 / ((double)nx * (double)ny)}, stream);
+}
+}  // namespace scint
+
+extern "C" int32_t scint_sim_screen_workspace_bytes(int64_t nx, int64_t ny, size_t* bytes) {
+    SCINT_REQUIRE(bytes != nullptr, "sim_screen_workspace_bytes: null output");
+    const int32_t rc = sim_check_shape(nx, ny);
+    if (rc != SCINT_OK) return rc;
+    *bytes = sizeof(cplx) * (size_t)(nx * ny) + 256;
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_sim_screen(const double* z1, const double* z2, int64_t nx, int64_t ny, double dqx, double dqy,
+                                    double a, double b, double c, double con, double alf, double inner2, double* w,
+                                    double* xyp, void* workspace, size_t workspace_bytes, void* stream_) {
+    SCINT_REQUIRE(z1 && z2 && w && xyp && workspace, "sim_screen: null pointer");
+    int32_t rc = sim_check_shape(nx, ny);
+    if (rc != SCINT_OK) return rc;
+    if (workspace_bytes < sizeof(cplx) * (size_t)(nx * ny)) { set_error("scint: sim_screen workspace too small"); return SCINT_E_WORKSPACE; }
+    hipStream_t stream = (hipStream_t)stream_;
+    cplx* work = (cplx*)workspace;
+    const SimScreenPar par{(int)nx, (int)ny, dqx, dqy, a, b, c, con, alf, inner2};
+    hipLaunchKernelGGL(sim_weights_kernel, dim3((unsigned)ceil_div(nx * ny, 256)), dim3(256), 0, stream, par, w);
+    SCINT_LAUNCH_CHECK();
+    rc = launch_fft_rows(ny, nx, SimScreenLoad{w, z1, z2, (int)ny}, SimRowStore{work, (int)ny}, stream);
+    if (rc != SCINT_OK) return rc;
+    ArrayLoad mid_ld{work, (int)ny, 0};
+    ArrayStore mid_st{work, (int)ny, 0};
+    return run_cols_fft(nx, ny, 1, mid_ld, mid_ld, mid_st, SimRealStore{xyp, (int)ny}, stream);
+}
+
+extern "C" int32_t scint_sim_field_workspace_bytes(int64_t nx, int64_t ny, int64_t group, size_t* bytes) {
+    SCINT_REQUIRE(bytes != nullptr, "sim_field_workspace_bytes: null output");
+    const int32_t rc = sim_check_shape(nx, ny);
+    if (rc != SCINT_OK) return rc;
+    SCINT_REQUIRE(group >= 1, "sim_field_workspace_bytes: a group holds at least one frequency");
+    *bytes = sim_freq_bytes(nx, ny) * (size_t)std::min(group, sim_group_max(nx)) + 768;
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_sim_last_route(int32_t* column, int64_t* groups) {
+    SCINT_REQUIRE(column && groups, "sim_last_route: null output");
+    *column = g_sim_column; *groups = g_sim_groups;
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_sim_field(const double* xyp, int64_t nx, int64_t ny, const double* scale, int64_t nf, int64_t f0,
+                                   int64_t f1, double ffconx, double ffcony, void* spe_, float* spi, double* xyi,
+                                   void* workspace, size_t workspace_bytes, void* stream_) {
+    SCINT_REQUIRE(xyp && scale && spe_ && spi && workspace, "sim_field: null pointer");
+    int32_t rc = sim_check_shape(nx, ny);
+    if (rc != SCINT_OK) return rc;
+    SCINT_REQUIRE(nf >= 1 && nf < (1 << 30) && f0 >= 0 && f0 < f1 && f1 <= nf, "sim_field: bad frequency range");
+    SCINT_REQUIRE((double)nx * (double)nf < 2147483648.0, "sim_field: nx * nf must stay below 2^31");
+    hipStream_t stream = (hipStream_t)stream_;
+    float* spe = (float*)spe_;
+    const size_t per = sim_freq_bytes(nx, ny);
+    const size_t usable = workspace_bytes >= 768 ? workspace_bytes - 768 : 0;
+    const int64_t G = std::min<int64_t>(std::min<int64_t>((int64_t)(usable / per), sim_group_max(nx)), f1 - f0);
+    if (G < 1) { set_error("scint: sim_field workspace holds no frequency"); return SCINT_E_WORKSPACE; }
+    Carver cv(workspace, workspace_bytes);
+    cplx* A = cv.take<cplx>((size_t)(G * nx * ny));
+    cplx* B = cv.take<cplx>((size_t)(G * nx * ny));
+    cplx* g = cv.take<cplx>((size_t)(G * nx));
+    if (!cv.ok()) { set_error("scint: sim_field workspace too small"); return SCINT_E_WORKSPACE; }
+    const char* env = getenv("SCINT_SIM_COLUMN");      // read per call: "0" = every frequency by the full inverse transform
+    const bool column = !(env && atoi(env) == 0);
+    g_sim_column = column ? 1 : 0;
+    g_sim_groups = 0;
+    const int64_t plane = nx * ny;
+    const double norm = 1.0 / ((double)nx * (double)ny);
+    for (int64_t f = f0; f < f1; f += G) {
+        const int64_t cnt = std::min(G, f1 - f);
+        ++g_sim_groups;
+        if (!column) {
+            rc = sim_full(xyp, scale, nx, ny, nf, f, cnt, ffconx, ffcony, spe, spi, xyi, A, B, stream);
+            if (rc != SCINT_OK) return rc;
+            continue;
+        }
+        rc = run_cols_fft(nx, ny, cnt, SimPhaseLoad{xyp, scale + f, (int)ny}, ArrayLoad{A, (int)ny, plane},
+                          ArrayStore{A, (int)ny, plane}, ArrayStore{B, (int)ny, plane}, stream);
+        if (rc != SCINT_OK) return rc;
+        const SimFilter filt{scale + f, ffconx, ffcony, (int)nx, (int)ny, ilog2(nx), cnt * nx};
+        rc = launch_fft_rows(ny, cnt * nx, SimRowLoad{B, (int)ny}, SimFilterReduce{filt, g, (int)cnt}, stream);
+        if (rc != SCINT_OK) return rc;
+        rc = run_cols_fft(nx, cnt, 1, ArrayLoad{g, (int)cnt, 0}, ArrayLoad{g, (int)cnt, 0}, ArrayStore{g, (int)cnt, 0},
+                          SimSpeStore{spe, spi, (int)nf, (int)f, norm}, stream);
+        if (rc != SCINT_OK) return rc;
+    }
+    if (column && xyi && f1 == nf)    // the intensity plane of the last frequency needs the whole inverse transform once
+        return sim_full(xyp, scale, nx, ny, nf, nf - 1, 1, ffconx, ffcony, nullptr, nullptr, xyi, A, B, stream);
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_sim_pulse(const void* spe, int64_t nx, int64_t nf, const double* window, double* out, void* stream_) {
+    SCINT_REQUIRE(spe && window && out, "sim_pulse: null pointer");
+    SCINT_REQUIRE(nx >= 1 && nx < (1 << 24), "sim_pulse: bad nx");
+    SCINT_REQUIRE(nf >= 8 && nf <= 4096 && is_pow2(nf), "sim_pulse: 2 nf must be a power of two in [16, 8192]");
+    return launch_fft_rows(2 * nf, nx, SimPulseLoad{(const float*)spe, window, (int)nf},
+                           SimPulseStore{out, (int)nf, nx * 2 * nf}, (hipStream_t)stream_);
 }

@@ -197,6 +197,12 @@ __device__ inline int stockham_out_index(int t, int Tr, int Ns, int q, int m) {
 // (fixed order: lanes, then waves) in st.partial[blockIdx.x]; the caller adds the partials in order.
 template <class S, class = void> struct IsReducing : std::false_type {};
 template <class S> struct IsReducing<S, std::void_t<decltype(S::kReduce)>> : std::true_type {};
+// A storer may also reduce every SLOT to one complex value: it declares `static constexpr bool kSlotReduce = true`, its
+// slot accessor takes a running complex sum -- sx(index, value, acc) -- and the kernel hands the slot's total to
+// sx.finish(total), called by ONE thread of the slot.  The order is fixed: each thread adds its sixteen outputs in
+// register order, then the slot's n/16 threads meet in a binary tree through LDS -- equal inputs give equal bits.
+template <class S, class = void> struct IsSlotReducing : std::false_type {};
+template <class S> struct IsSlotReducing<S, std::void_t<decltype(S::kSlotReduce)>> : std::true_type {};
 
 // Stage sequence R0,R1,R2,R3 (1 = unused); product = n.
 // SPLIT: the stage exchanges move the real parts, then the imaginary parts, through an LDS buffer of
@@ -317,6 +323,24 @@ fft_rows_kernel(RowShape sh, Loader ld, Storer st) {
             for (int k = t; k <= n / 2; k += Tr)
                 sx.pair(k, lds[lds_pad(k)], lds[lds_pad((n - k) & (n - 1))]);
         }
+    } else if constexpr (IsSlotReducing<Storer>::value) {
+        cplx acc = mk(0.0, 0.0);
+        if (active) {
+#pragma unroll
+            for (int q = 0; q < kEPT / RL; ++q)
+#pragma unroll
+                for (int m = 0; m < RL; ++m)
+                    sx(stockham_out_index<RL>(t, Tr, Ns, q, m), v[q * RL + m], acc);
+        }
+        // one partial per thread into the exchange buffer (blockDim.x values: it holds more than that in either form)
+        __syncthreads();
+        smem[threadIdx.x] = acc;
+        __syncthreads();
+        for (int s = Tr >> 1; s > 0; s >>= 1) {
+            if (t < s) smem[threadIdx.x] = smem[threadIdx.x] + smem[threadIdx.x + s];
+            __syncthreads();
+        }
+        if (active && t == 0) sx.finish(smem[threadIdx.x]);
     } else if constexpr (IsReducing<Storer>::value) {
         __shared__ double red_[16];
         double acc = 0.0;
