@@ -583,6 +583,29 @@ int32_t scint_sim_field(const double* xyp, int64_t nx, int64_t ny, const double*
 int32_t scint_sim_last_route(int32_t* column /*HOST*/, int64_t* groups /*HOST*/);
 int32_t scint_sim_pulse(const void* spe, int64_t nx, int64_t nf, const double* window, double* out, void* stream);
 
+/* ---- theoretical 2-D ACF model: scint_sim.ACF (scint_sim.py:417-766; Rickett et al. 2014, Appendix A) ---------------------
+ * The strong-scintillation intensity ACF behind scint_models.scint_acf_model_2d.  For every frequency lag dnun[idn], idn >= 1,
+ * and every time-lag sample s the reference sums gammes[y][x] exp(i ((X - sx)^2 + (Y - sy)^2) / (2 dnun[idn])) over a square
+ * grid; here the phase is factorised into exp(i (X - sx)^2 / (2 nu)) exp(i (Y - sy)^2 / (2 nu)) and the sum over x becomes a
+ * real x complex float64 matrix product on the matrix cores (csrc/acf.hpp).  Grid lengths are DATA: the host builds the axes
+ * with NumPy (np.arange with a float step) and passes their lengths.
+ * scint_acf_model: inputs (device) snp[m] the coarse grid, snp2[m2] the core grid (lag 1 only), snx[nsn], sny[nsn] the time-lag
+ *   samples in the screen's coordinates, dnun[ndnun] the frequency lags (dnun[0] = 0 is not read); sigxn, sigyn the phase
+ *   gradient (the centres of lag idn are snx - 2 sigxn dnun[idn], sny - 2 sigyn dnun[idn]); sqrtar = sqrt(ar), alph2 = alpha / 2;
+ *   step = dsp / res_fac the coarse grid's step, step2 = dsp / core_fac the core grid's.
+ *   Outputs (device): gammes[m][m] = exp(-0.5 ((x / sqrtar)^2 + (y sqrtar)^2)^alph2), x = snp[column], y = snp[row] (the
+ *   reference's acf_efield), and the complex field gamma[nsn][ndnun], columns 1 .. ndnun - 1:
+ *   gamma[s][idn] = -i step^2 / (2 pi dnun[idn]) sum_yx G exp(i ...) with the core grid for idn = 1.  Column 0 (dnun = 0) is NOT
+ *   written: it is the e-field ACF at the samples, which the host computes.  Any m, m2, nsn >= 1 and ndnun >= 2 (m, m2 <= 2^24,
+ *   nsn <= 64 * 65535, ndnun <= 65536).  Five launches (four when ndnun == 2); no atomics: results are bit-reproducible.
+ *   Asynchronous on `stream`.  Workspace: scint_acf_model_workspace_bytes(m, m2, nsn, ndnun) -- the phase tables
+ *   (32 nsnp (m2 + (ndnun - 2) m) bytes, nsnp = nsn rounded up to 16) and one partial per (lag, block of 64 rows, s). */
+int32_t scint_acf_model_workspace_bytes(int64_t m, int64_t m2, int64_t nsn, int64_t ndnun, size_t* bytes /*HOST*/);
+int32_t scint_acf_model(const double* snp, int64_t m, const double* snp2, int64_t m2, const double* snx,
+                        const double* sny, int64_t nsn, const double* dnun, int64_t ndnun, double sigxn, double sigyn,
+                        double sqrtar, double alph2, double step, double step2, double* gammes, scint_c128* gamma,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- thin-screen curvature search: two_curve_map + singularvalue_calc (ththmod.py:496-513, 1557-1636) ----------------
  * The 'thin' fitting procedure of Dynspec.prep_thetatheta (dynspec.py:1480-1516) models only the region near the arclet apexes:
  * a RECTANGULAR theta-theta map thth[theta2, theta1] (rows: the arclet centres th2[M2], columns: the main-arc centres th1[M1],

@@ -819,3 +819,60 @@ extern "C" int32_t scint_mosaic_fit_hess(const scint_c128* chunks, int64_t ncf, 
     SCINT_LAUNCH_CHECK();
     return SCINT_OK;
 }
+
+// ---- the theoretical 2-D ACF model (scint_sim.py:417-766, ACF.calc_acf): kernels in acf.hpp ------------------------------------
+#include "acf.hpp"
+
+namespace scint {
+static bool acf_shape_ok(int64_t m, int64_t m2, int64_t nsn, int64_t ndnun) {
+    // grid limits of acf_contract_kernel (y: chunks of 64 columns, z: lags) and 32-bit row indices
+    return m >= 1 && m2 >= 1 && nsn >= 1 && ndnun >= 2 && m <= (1 << 24) && m2 <= (1 << 24) && nsn <= 64 * 65535 && ndnun <= 65536;
+}
+static void acf_sizes(int64_t m, int64_t m2, int64_t nsn, int64_t ndnun, size_t* tab, size_t* part) {
+    const int64_t nsnp = ceil_div(nsn, 16) * 16;
+    *tab = (size_t)(4 * nsnp * (m2 + (ndnun - 2) * m));
+    *part = (size_t)(nsnp * (ceil_div(m2, kAcfRows) + (ndnun - 2) * ceil_div(m, kAcfRows)));
+}
+}  // namespace scint
+
+extern "C" int32_t scint_acf_model_workspace_bytes(int64_t m, int64_t m2, int64_t nsn, int64_t ndnun, size_t* bytes) {
+    SCINT_REQUIRE(bytes != nullptr, "acf_model_workspace_bytes: null output");
+    SCINT_REQUIRE(acf_shape_ok(m, m2, nsn, ndnun), "acf_model_workspace_bytes: bad shape (m, m2, nsn >= 1, ndnun >= 2)");
+    size_t tab = 0, part = 0;
+    acf_sizes(m, m2, nsn, ndnun, &tab, &part);
+    *bytes = align_up(sizeof(double) * tab, 256) + align_up(sizeof(cplx) * part, 256) + 256;
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_acf_model(const double* snp, int64_t m, const double* snp2, int64_t m2, const double* snx, const double* sny,
+                                   int64_t nsn, const double* dnun, int64_t ndnun, double sigxn, double sigyn, double sqrtar,
+                                   double alph2, double step, double step2, double* gammes, scint_c128* gamma, void* workspace,
+                                   size_t workspace_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    SCINT_REQUIRE(snp && snp2 && snx && sny && dnun && gammes && gamma && workspace, "acf_model: null pointer");
+    SCINT_REQUIRE(acf_shape_ok(m, m2, nsn, ndnun), "acf_model: bad shape (m, m2, nsn >= 1, ndnun >= 2)");
+    size_t need = 0, tab = 0, part = 0;
+    if (scint_acf_model_workspace_bytes(m, m2, nsn, ndnun, &need) != SCINT_OK) return SCINT_E_ARG;
+    if (workspace_bytes < need) { set_error("scint: acf_model workspace too small"); return SCINT_E_WORKSPACE; }
+    acf_sizes(m, m2, nsn, ndnun, &tab, &part);
+    Carver carve(workspace, workspace_bytes);
+    AcfPar p;
+    p.snp = snp; p.snp2 = snp2; p.snx = snx; p.sny = sny; p.dnun = dnun;
+    p.m = (int)m; p.m2 = (int)m2; p.nsn = (int)nsn; p.nsnp = (int)(ceil_div(nsn, 16) * 16); p.ndnun = (int)ndnun;
+    p.sigxn = sigxn; p.sigyn = sigyn; p.sqrtar = sqrtar; p.alph2 = alph2; p.step = step; p.step2 = step2;
+    p.gammes = gammes;
+    p.tab = carve.take<double>(tab);
+    p.part = carve.take<cplx>(part);
+    p.gamma = (cplx*)gamma;
+    const int64_t ntab = (int64_t)tab / 2;                                   // one thread per (row, axis, s): a re and an im each
+    const unsigned chunks = (unsigned)ceil_div(p.nsnp, 16 * kAcfGroups);
+    SCINT_REQUIRE(ceil_div(ntab, 256) < (int64_t(1) << 31) && ceil_div(m * m, 256) < (int64_t(1) << 31), "acf_model: grids too large");
+    hipLaunchKernelGGL(acf_efield_kernel, dim3((unsigned)ceil_div(m * m, 256)), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(acf_tables_kernel, dim3((unsigned)ceil_div(ntab, 256)), dim3(256), 0, stream, p, ntab);
+    hipLaunchKernelGGL(acf_contract_kernel<true>, dim3((unsigned)acf_yblocks(p.m2), chunks, 1), dim3(256), 0, stream, p, 1);
+    if (ndnun > 2)
+        hipLaunchKernelGGL(acf_contract_kernel<false>, dim3((unsigned)acf_yblocks(p.m), chunks, (unsigned)(ndnun - 2)), dim3(256), 0, stream, p, 2);
+    hipLaunchKernelGGL(acf_finish_kernel, dim3((unsigned)ceil_div((ndnun - 1) * nsn, 256)), dim3(256), 0, stream, p);
+    SCINT_LAUNCH_CHECK();
+    return SCINT_OK;
+}

@@ -19,8 +19,18 @@ most 65535 butterflies in its grid -- 2**18 would end on a radix-4 pass of 65536
 power of two in [16, 8192] (the contiguous axis: the row kernel, launch_fft_rows), ``nx * ny <= 2**28``, ``nf >= 2``
 arbitrary; anything else raises ``ValueError``.  ``pulsewin`` needs ``2 * nf`` to be a power of two in [16, 8192] and
 raises ``NotImplementedError`` otherwise.
+
+``ACF`` is the reference's theoretical 2-D intensity ACF (scint_sim.py:417-766; Rickett et al. 2014, Appendix A), the model of
+``scint_models.scint_acf_model_2d``:
+
+    from scintools_amd.scint_sim import ACF
+    model = ACF(ar=3, psi=30, phasegrad=0.5, theta=40, taumax=4, dnumax=4, nt=51, nf=51).acf
+
+Its Fresnel sums run as one float64 matrix-core contraction per frequency lag (csrc/acf.hpp, entry point scint_acf_model;
+DESIGN.md, "The 2-D ACF model"); the axes, the ``dnun = 0`` column and the mirroring are the reference's NumPy lines on the host.
 """
 import ctypes
+import warnings
 
 import numpy as np
 import scipy.constants as sc
@@ -257,3 +267,160 @@ class Simulation:
             self.get_pulse()
             return self.__dict__[name]
         raise AttributeError(f"'{type(self).__name__}' object has no attribute '{name}'")
+
+
+class ACF:
+    """The reference's ``ACF``: same arguments, same attributes (``alpha, ar, psi, phasegrad, theta, amp, wn, taumax, dnumax, nf, nt,
+    sp_fac, res_fac, core_fac, dsp, ddnun``; ``fn, tn, sn, snp, acf, acf_efield``; ``sspec`` after ``calc_sspec``).  The sums over the
+    spatial grids -- every ``dnun > 0`` column of the field -- and ``acf_efield`` come from the device (scint_acf_model); the complex
+    field before ``real(g * conj(g))`` is kept as ``gammitv``.  ``plot=True`` and the ``plot_*`` methods warn and draw nothing.  Sizes
+    the reference cannot compute raise what it raises: ``nf = 1`` an ``IndexError`` (``dnun[1]``), ``nt = 1`` a
+    ``ZeroDivisionError`` (``dsp``); 2 is made odd first, as every even size, and computes."""
+
+    def __init__(self, psi=0, phasegrad=0, theta=0, ar=1, alpha=5 / 3, taumax=4, dnumax=4, nf=51, nt=51, amp=1, wn=0,
+                 spatial_factor=2, resolution_factor=1, core_factor=2, auto_sampling=True, plot=False, display=True):
+        self.alpha = alpha
+        self.ar = ar
+        self.psi = psi
+        self.phasegrad = phasegrad
+        self.theta = theta
+        self.amp = amp
+        self.wn = wn
+        self.taumax = taumax
+        spmax = taumax
+        self.dnumax = dnumax
+        if nf % 2 == 0:
+            nf += 1
+        if nt % 2 == 0:
+            nt += 1
+        self.nf = nf
+        self.nt = nt
+        if auto_sampling:                                                # scint_sim.py:471-481
+            self.sp_fac = 6 * ar / spmax
+            self.res_fac = 1 + ar / 3
+            self.core_fac = 4
+        else:
+            self.sp_fac = spatial_factor
+            self.res_fac = resolution_factor
+            self.core_fac = core_factor
+        self.dsp = 4 * spmax / (nt - 1)
+        self.calc_acf()
+        if plot:
+            self.plot_acf(display=display)
+
+    def calc_acf(self, plot=False):
+        """The ACF of intensity against time and frequency lag (scint_sim.py:494-678).  Host: the axes (NumPy decides their lengths),
+        the ``dnun = 0`` column, the white-noise spike, ``real(g * conj(g))``, the mirroring and ``amp``.  Device: ``acf_efield`` and
+        every other column of the field."""
+        alph2 = self.alpha / 2
+        spmax = self.taumax
+        dnumax = self.dnumax
+        dsp = self.dsp
+        phasegrad = self.phasegrad
+        theta = self.theta
+        amp = self.amp
+        wn = self.wn
+        xi = 90 - self.psi
+        Vx = np.cos(xi * np.pi / 180)
+        Vy = np.sin(xi * np.pi / 180)
+        sigxn = phasegrad * np.cos((xi - theta) * np.pi / 180)
+        sigyn = phasegrad * np.sin((xi - theta) * np.pi / 180)
+        ar = self.ar
+        sqrtar = np.sqrt(ar)
+        dnun = np.linspace(0, dnumax, int(np.ceil(self.nf / 2)))
+        ddnun = np.abs(dnun[1] - dnun[0])
+        self.ddnun = ddnun
+        ndnun = len(dnun)
+        sp_fac = self.sp_fac
+        res_fac = self.res_fac
+        core_fac = self.res_fac * self.core_fac
+        snp = np.arange(-sp_fac * spmax, sp_fac * spmax + dsp / res_fac, dsp / res_fac)
+        snp2 = np.arange(-sp_fac * spmax, sp_fac * spmax + dsp / core_fac, dsp / core_fac)
+        if phasegrad == 0:
+            tn = np.linspace(0, (spmax), int(np.ceil(self.nt / 2)))
+            snx = Vx * tn
+            sny = Vy * tn
+            sigxn = sigyn = 0.0                                          # this branch of the reference does not shift the centres
+        else:
+            tn = np.linspace(-(spmax), (spmax), self.nt)
+            snx = np.cos(xi * np.pi / 180) * tn
+            sny = np.sin(xi * np.pi / 180) * tn
+        gammitv = np.zeros((int(len(snx)), int(ndnun)), dtype=np.complex128)
+        gammitv[:, 0] = np.exp(-0.5 * ((snx / sqrtar)**2 + (sny * sqrtar)**2)**alph2)
+        if phasegrad == 0:
+            gammitv[0, 0] += wn / amp
+        else:
+            gammitv[np.argwhere(snx == 0), 0] += wn / amp
+        field, gammes = self._device_field(snp, snp2, snx, sny, dnun, float(sigxn), float(sigyn), float(sqrtar), float(alph2),
+                                           float(dsp / res_fac), float(dsp / core_fac))
+        gammitv[:, 1:] = field[:, 1:]
+        self.gammitv = gammitv
+        # equation A1 convert ACF of E to ACF of I
+        gammitv = np.real(gammitv * np.conj(gammitv))
+        nr, nc = np.shape(gammitv)
+        if phasegrad == 0:
+            gam2 = np.zeros((nr, nc * 2 - 1))
+            gam2[:, 0:nc - 1] = np.fliplr(gammitv[:, 1:])
+            gam2[:, nc - 1:] = gammitv
+            gam2 = gam2.squeeze()
+            gam3 = np.zeros((nr * 2 - 1, nc * 2 - 1))
+            gam3[0:nr - 1, :] = np.flipud(gam2[1:, :])
+            gam3[nr - 1:, :] = gam2
+            gam3 = np.transpose(gam3)
+            t2 = np.concatenate((np.flip(-tn[1:]), tn)).squeeze()
+            f2 = np.concatenate((np.flip(-dnun[1:]), dnun)).squeeze()
+        else:
+            gam3 = np.zeros((nr, nc * 2 - 1))
+            gam3[:, 0:nc - 1] = np.fliplr(np.flipud(gammitv[:, 1:]))
+            gam3[:, nc - 1:] = gammitv
+            gam3 = np.transpose(gam3)
+            f2 = np.concatenate((np.flip(-dnun[1:]), dnun)).squeeze()
+            t2 = tn
+        self.fn = f2
+        self.tn = t2
+        self.sn = t2
+        self.snp = snp
+        self.acf = amp * gam3
+        self.acf_efield = gammes
+        if plot:
+            self.plot_acf()
+
+    @staticmethod
+    def _device_field(snp, snp2, snx, sny, dnun, sigxn, sigyn, sqrtar, alph2, step, step2):
+        """(field [nsn, ndnun] complex128 with column 0 left at zero, acf_efield [m, m]) from scint_acf_model."""
+        dev = device.require_gpu()
+        lib = _lib.load()
+        m, m2, nsn, ndnun = len(snp), len(snp2), len(snx), len(dnun)
+        need = ctypes.c_size_t()
+        _lib.check(lib.scint_acf_model_workspace_bytes(m, m2, nsn, ndnun, ctypes.byref(need)), "scint_acf_model_workspace_bytes")
+        ws = device.workspace.get(need.value)
+        d_snp, d_snp2, d_snx, d_sny, d_dnun = (device.to_device(a, torch.float64) for a in (snp, snp2, snx, sny, dnun))
+        gammes = torch.empty((m, m), dtype=torch.float64, device=dev)
+        gamma = torch.zeros((nsn, ndnun), dtype=torch.complex128, device=dev)
+        _lib.check(lib.scint_acf_model(device.ptr(d_snp), m, device.ptr(d_snp2), m2, device.ptr(d_snx), device.ptr(d_sny), nsn,
+                                       device.ptr(d_dnun), ndnun, sigxn, sigyn, sqrtar, alph2, step, step2, device.ptr(gammes),
+                                       device.ptr(gamma), device.ptr(ws), need.value, device.stream_ptr()), "scint_acf_model")
+        return gamma.cpu().numpy(), gammes.cpu().numpy()
+
+    def calc_sspec(self, window='hanning', window_frac=1):
+        """The secondary spectrum of the model ACF (scint_sim.py:728-742).  Host NumPy, as in the reference: an odd-length
+        transform of the small ``nf x nt`` model array (at most a few hundred points a side), not a hot path."""
+        from .dynspec import get_window
+        nf, nt = np.shape(self.acf)
+        chan_window, subint_window = get_window(nt, nf, window=window, frac=window_frac)
+        arr = np.multiply(chan_window, self.acf)
+        arr = np.transpose(np.multiply(subint_window, np.transpose(arr)))
+        arr = np.fft.fftshift(arr)
+        arr = np.fft.fft2(arr)
+        arr = np.fft.fftshift(arr)
+        arr = np.sqrt(np.real(arr * np.conj(arr)))
+        self.sspec = 10 * np.log10(arr)
+
+    def plot_acf(self, *args, **kwargs):
+        warnings.warn("ACF.plot_acf: plotting is outside the accelerated hot path; nothing is drawn")
+
+    def plot_acf_efield(self, *args, **kwargs):
+        warnings.warn("ACF.plot_acf_efield: plotting is outside the accelerated hot path; nothing is drawn")
+
+    def plot_sspec(self, *args, **kwargs):
+        warnings.warn("ACF.plot_sspec: plotting is outside the accelerated hot path; nothing is drawn")
