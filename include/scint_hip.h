@@ -647,6 +647,29 @@ int32_t scint_sv_sweep_multi(const scint_c128* cs_stack, int64_t ncs, int64_t cs
                              double* sv_out, int32_t* status_out, int32_t* iters_out,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Scattered image: Dynspec.calc_scattered_image (dynspec.py:3553-3570) -- scipy's RectBivariateSpline(tdel, fdop, 10**(sspec/10))
+ * (kx = ky = 3, s = 0: the tensor-product not-a-knot interpolating cubic spline), evaluated at ((fx[j]^2 + fy[i]^2) eta, fx[j]) with
+ * both arguments clamped to the knots, times fy[i], mirrored into image[nx][nx] (nx = 2 sampling + 1, ny = sampling + 1 rows computed).
+ * sspec_db: the dB spectrum with leading dimension ld; the crop is rows [row0, row1) x columns [col0, col1), at least 4 x 4.
+ * Everything the host decides is data: tdel[nrow] the cropped row knots (strictly increasing, any spacing);
+ *   row_sys[4][ncol] = 1/h, 6/pivot, -sub/pivot, sup of the column-axis (Doppler) not-a-knot system in second-derivative form and
+ *   row_end[4] (HOST) its end rule M[0] = e0 M[1] + e1 M[2], M[n-1] = e2 M[n-2] + e3 M[n-3]; row_warm the warm-up length of a row
+ *   chunk (rows of more than 2050 knots are solved in chunks; 1..256, unused for shorter rows); row_idx[nx], row_coef[nx][4] the
+ *   interval and the weights of y[k], y[k+1], M[k], M[k+1] of the clamped abscissa fx[j] on the Doppler knots;
+ *   col_sys[4][nrow] = h, sub, 1/pivot, sup of the delay-axis system, col_end[4] (HOST), col_block_rows / col_warm its blocking as in
+ *   scint_spline_resample (0, 0: one sequential sweep); fx[nx], fy[ny] the image axes (not clamped).
+ * Outputs (device): image[nx][nx]; *nonfinite = 1 if some 10**(v/10) of the crop is NaN or inf (scipy then returns NaN everywhere),
+ *   else 0.  No atomics: equal inputs give equal bits.  Asynchronous on `stream`.
+ * Workspace: scint_scattered_image_workspace_bytes(nrow, sampling): three nrow x nx planes. */
+int32_t scint_scattered_image_workspace_bytes(int64_t nrow, int64_t sampling, size_t* bytes /*HOST*/);
+int32_t scint_scattered_image(const double* sspec_db, int64_t ld, int64_t row0, int64_t row1, int64_t col0, int64_t col1,
+                              const double* tdel, const double* row_sys, const double* row_end /*HOST[4]*/, int64_t row_warm,
+                              const int32_t* row_idx, const double* row_coef, const double* col_sys,
+                              const double* col_end /*HOST[4]*/, int64_t col_block_rows, int64_t col_warm,
+                              const double* fx, const double* fy, double eta, int64_t sampling, double* image,
+                              int32_t* nonfinite, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -139,6 +139,9 @@ _SIGNATURES = {
     "scint_acf_model_workspace_bytes": ([c_int64, c_int64, c_int64, c_int64, POINTER(c_size_t)], c_int32),
     "scint_acf_model": ([_P, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_double, c_double, c_double, c_double, c_double,
                          c_double, _P, _P, _P, c_size_t, _P], c_int32),
+    "scint_scattered_image_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
+    "scint_scattered_image": ([_P, c_int64, c_int64, c_int64, c_int64, c_int64, _P, _P, POINTER(c_double), c_int64, _P, _P, _P,
+                               POINTER(c_double), c_int64, c_int64, _P, _P, c_double, c_int64, _P, _P, _P, c_size_t, _P], c_int32),
 }
 
 _lib = None

@@ -12,6 +12,7 @@ reference.  Plotting, ``velocity`` scaling, ``interp_nan`` (scipy griddata) and
 ``fit_spectrum`` (lmfit) are outside the accelerated path and raise ``NotImplementedError``.
 """
 import ctypes
+import warnings
 
 import numpy as np
 import scipy.constants as sc
@@ -75,6 +76,15 @@ def _spline_blocks(sub, inv, sup, n):
     rows = n - 2
     if rows < 4 * _SPLINE_BLOCK_ROWS:
         return 0, 0
+    warm = _spline_warm(sub, inv, sup, n)
+    if warm > 2 * _SPLINE_BLOCK_ROWS:
+        return 0, 0
+    return _SPLINE_BLOCK_ROWS, int(warm)
+
+
+def _spline_warm(sub, inv, sup, n):
+    """The shortest run of rows (a multiple of 8) over which every window of forward and of backward Thomas factors
+    multiplies to < 1e-22: the warm-up after which a sweep started from zero has forgotten its start."""
     tiny = 1e-300                                              # an exact zero factor (uniform ends) decouples
     lf = np.log(np.maximum(np.abs(sub[2:n - 1] * inv[2:n - 1]), tiny))   # forward factors, rows 2..n-2
     lb = np.log(np.maximum(np.abs(sup[1:n - 2]), tiny))                   # backward factors, rows 1..n-3
@@ -86,9 +96,7 @@ def _spline_blocks(sub, inv, sup, n):
         while w < len(lg) and np.max(c[w:] - c[:-w]) > target:
             w += 8
         warm = max(warm, w)
-    if warm > 2 * _SPLINE_BLOCK_ROWS:
-        return 0, 0
-    return _SPLINE_BLOCK_ROWS, int(warm)
+    return warm
 
 
 def spline_resample_device(dyn_t, freqs, feq):
@@ -501,3 +509,166 @@ def fit_arc(self, asymm=False, plot=False, delmax=None, numsteps=1e4, startbin=3
             self.norm_delmax = delmax
     finally:
         self._arc_dev_cache = None
+
+
+# ----------------------------------------------------------------------------
+# calc_scattered_image
+# ----------------------------------------------------------------------------
+_SCAT_REGION = 2048        # knots one workgroup of pass A solves (csrc/scatim.hpp, kScatRegion)
+_SCAT_MAX_WARM = 256
+
+
+def _check_spline_axes(x, y, shape):
+    """What scipy's RectBivariateSpline(x, y, z) (kx = ky = 3) raises for these axes and this z.shape, in its order."""
+    if not np.all(np.diff(x) > 0.0):
+        raise ValueError('x must be strictly increasing')
+    if not np.all(np.diff(y) > 0.0):
+        raise ValueError('y must be strictly increasing')
+    if not x.size == shape[0]:
+        raise ValueError('x dimension of z must have same number of elements as x')
+    if not y.size == shape[1]:
+        raise ValueError('y dimension of z must have same number of elements as y')
+    if x.size < 4 or y.size < 4:
+        # FITPACK's own error (its type is private to scipy): let scipy raise it, on zeros of the offending size
+        from scipy.interpolate import RectBivariateSpline
+        mx, my = min(x.size, 4), min(y.size, 4)
+        RectBivariateSpline(np.arange(float(mx)), np.arange(float(my)), np.zeros((mx, my)))
+        raise ValueError("RectBivariateSpline needs at least 4 points per axis")      # not reached with the scipy in use
+
+
+def scattered_image_device(sspec_t, rows, cols, tdel, fdop, eta, sampling):
+    """image[nx, nx] of ``calc_scattered_image`` from the dB spectrum on the device, cropped to rows [rows[0], rows[1]) and columns
+    [cols[0], cols[1]), with the cropped knots tdel / fdop (any strictly increasing spacing): the interpolating bicubic
+    not-a-knot spline of 10**(sspec/10) evaluated through eta, times fdop_y, mirrored (``scint_scattered_image``).  Returns
+    (image, fdop_x).  The Thomas factors, the intervals and the abscissae are host NumPy, handed over as data."""
+    lib = _lib.load()
+    require_gpu()
+    tdel = np.ascontiguousarray(tdel, dtype=float)
+    fdop = np.ascontiguousarray(fdop, dtype=float)
+    nrow, n = int(rows[1] - rows[0]), int(cols[1] - cols[0])
+    _check_spline_axes(tdel, fdop, (max(nrow, 0), max(n, 0)))
+    if sspec_t.stride(1) != 1:
+        sspec_t = sspec_t.contiguous()
+    nx, ny = 2 * sampling + 1, sampling + 1
+    fdop_x = np.linspace(-max(fdop), max(fdop), nx)
+    fdop_y = np.linspace(0, max(fdop), ny)
+    # Doppler axis: factors in the form pass A consumes, intervals and weights of the clamped abscissae (bispev clamps)
+    h, sub, inv, sup, end = _spline_system(fdop)
+    row_sys = np.zeros((4, n))
+    row_sys[0, :n - 1] = 1.0 / h
+    row_sys[1] = 6.0 * inv
+    row_sys[2] = -sub * inv
+    row_sys[3] = sup
+    row_warm = 0
+    if n - 2 > _SCAT_REGION:
+        row_warm = _spline_warm(sub, inv, sup, n) + 2
+        if row_warm > _SCAT_MAX_WARM:
+            raise ValueError("calc_scattered_image: the Doppler axis is too irregular for the chunked spline solve")
+    xe = np.clip(fdop_x, fdop[0], fdop[-1])
+    idx = np.clip(np.searchsorted(fdop, xe, side="right") - 1, 0, n - 2)
+    hk = h[idx]
+    a = (fdop[idx + 1] - xe) / hk
+    b = (xe - fdop[idx]) / hk
+    coef = np.stack([a, b, (a**3 - a) * hk**2 / 6.0, (b**3 - b) * hk**2 / 6.0], axis=1)
+    # delay axis: the factors of scint_spline_resample's sweeps
+    hc, subc, invc, supc, endc = _spline_system(tdel)
+    col_sys = np.zeros((4, nrow))
+    col_sys[0, :nrow - 1] = hc
+    col_sys[1], col_sys[2], col_sys[3] = subc, invc, supc
+    block_rows, col_warm = _spline_blocks(subc, invc, supc, nrow)
+    dev = lambda v: to_device(np.ascontiguousarray(v, dtype=float), torch.float64)
+    tdel_t, row_sys_t, coef_t, col_sys_t, fx_t, fy_t = dev(tdel), dev(row_sys), dev(coef), dev(col_sys), dev(fdop_x), dev(fdop_y)
+    idx_t = to_device(idx.astype(np.int32), torch.int32)
+    need = ctypes.c_size_t()
+    _lib.check(lib.scint_scattered_image_workspace_bytes(nrow, sampling, ctypes.byref(need)), "scattered_image_workspace_bytes")
+    ws = workspace.get(need.value)
+    image_t = empty((nx, nx), torch.float64)
+    flag_t = empty((1,), torch.int32)
+    as_c = lambda v: v.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    end, endc = np.ascontiguousarray(end, dtype=float), np.ascontiguousarray(endc, dtype=float)
+    rc = lib.scint_scattered_image(ptr(sspec_t), int(sspec_t.stride(0)), int(rows[0]), int(rows[1]), int(cols[0]), int(cols[1]),
+                                   ptr(tdel_t), ptr(row_sys_t), as_c(end), int(row_warm), ptr(idx_t), ptr(coef_t), ptr(col_sys_t),
+                                   as_c(endc), int(block_rows), int(col_warm), ptr(fx_t), ptr(fy_t), float(eta), int(sampling),
+                                   ptr(image_t), ptr(flag_t), ptr(ws), ws.numel(), stream_ptr())
+    _lib.check(rc, "scint_scattered_image")
+    image = image_t.cpu().numpy()
+    if int(flag_t.cpu().numpy()[0]):
+        # a NaN or inf in 10**(sspec/10): FITPACK's global solve spreads it over every coefficient and scipy returns NaN
+        # everywhere without raising; the blocked device solve would confine it, so the flag decides
+        image[:] = np.nan
+    return image, fdop_x
+
+
+def calc_scattered_image(self, input_sspec=None, input_eta=None, input_fdop=None, input_tdel=None, sampling=64,
+                         lamsteps=False, trap=False, ref_freq=1400, clean=True, s=None, veff=None, d=None, fit_arc=True,
+                         plot_fit=False, plot=False, plot_log=True, use_angle=False, use_spatial=False):
+    """The scattered image B(theta_x, theta_y) from the secondary spectrum and the arc curvature (dynspec.py:3412-3582), assuming
+    the primary arc; the x axis is aligned with the velocity.  Sets ``scattered_image`` ([2 sampling + 1] squared, float64) and
+    ``scattered_image_ax``.  The host lines are the reference's, in its order; the spline interpolation of 10**(sspec/10)
+    (scipy RectBivariateSpline) runs on the device, on a parked spectrum without a host copy.
+
+    * ``input_sspec`` may be a NumPy array or a device tensor (dB), with ``input_fdop`` / ``input_tdel``.
+    * ``clean`` is accepted and does nothing: the reference's block fills a copy of ``sspec`` that nothing reads afterwards
+      (``linsspec`` is formed before it) and swallows its own exceptions.
+    * When the curvature is so small that the arc stays inside the delay range at the first Doppler bin (``flim == 0``) the
+      reference crops the delay rows and takes ``tdel = fdop[:tlim]`` -- the Doppler axis -- as their knots (dynspec.py:3521).
+      That is reproduced as it stands, wrong axis included.
+    * A NaN or +inf pixel in the cropped 10**(sspec/10) gives an all-NaN image and no exception, as scipy does; -inf dB is an exact 0.
+    * ``trap``, ``plot`` and ``plot_fit`` raise ``NotImplementedError``; the default ``plot_log=True`` only warns that nothing is drawn.
+    """
+    if plot or plot_fit:
+        raise NotImplementedError("plotting is outside the accelerated hot path")
+    if trap:
+        raise NotImplementedError("velocity / trap need Dynspec.scale_dyn('velocity'/'trapezoid'), "
+                                  "which is outside the accelerated hot path")
+    cls = type(self)
+    if input_sspec is None:
+        if lamsteps:
+            if not cls.lamsspec.present(self):
+                self.calc_sspec(lamsteps=lamsteps)
+            sspec_t = cls.lamsspec.tensor(self)
+        else:
+            if not cls.sspec.present(self):
+                self.calc_sspec(lamsteps=lamsteps)
+            sspec_t = cls.sspec.tensor(self)
+        fdop = np.array(self.fdop)
+        tdel = np.array(self.tdel)
+    else:
+        sspec_t = to_device(input_sspec, torch.float64)
+        fdop = input_fdop
+        tdel = input_tdel
+    nf, nt = len(fdop), len(tdel)
+    if input_eta is None and fit_arc:
+        if not hasattr(self, 'betaeta') and not hasattr(self, 'eta'):
+            self.fit_arc(lamsteps=lamsteps, log_parabola=True)
+        if lamsteps:
+            c = 299792458.0  # m/s
+            beta_to_eta = c * 1e6 / ((ref_freq * 1e6)**2)
+            eta = self.betaeta / (self.freq / ref_freq)**2     # correct for freq
+            eta = eta * beta_to_eta
+        else:
+            eta = self.eta
+    else:
+        if input_eta is None:
+            eta = tdel[nt - 1] / fdop[nf - 1]**2
+        else:
+            eta = input_eta
+    # crop sspec to desired region: Python's slice semantics on the spectrum's own shape and on the axes
+    nrow_all, ncol_all = (int(v) for v in sspec_t.shape)
+    flim = next(i for i, delay in enumerate(eta * fdop**2) if delay < np.max(tdel))
+    if flim == 0:
+        tlim = next(i for i, delay in enumerate(tdel) if delay > eta * fdop[0] ** 2)
+        rows = range(nrow_all)[:tlim]
+        cols = range(ncol_all)
+        tdel = fdop[:tlim]
+    else:
+        rows = range(nrow_all)
+        cols = range(ncol_all)[flim - int(0.02 * nf):nf - flim + int(0.02 * nf)]
+        fdop = fdop[flim - int(0.02 * nf):nf - flim + int(0.02 * nf)]
+    scat_im, xyaxes = scattered_image_device(sspec_t, (rows.start, max(rows.stop, rows.start)),
+                                             (cols.start, max(cols.stop, cols.start)), tdel, fdop, eta, sampling)
+    if plot_log:
+        warnings.warn("scintools_amd: calc_scattered_image does not draw the image (plot_log=True); "
+                      "it is in self.scattered_image")
+    self.scattered_image = scat_im
+    self.scattered_image_ax = xyaxes

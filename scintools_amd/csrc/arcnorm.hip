@@ -5,6 +5,7 @@
 //   scint_masked_colavg    np.ma.average(..., axis=0, weights)  dynspec.py:2171-2181
 //   scint_row_nanmean      delay response of subtract_artefacts dynspec.py:2060-2061
 //   scint_block_std        fit_arc's noise estimate             dynspec.py:1097-1101
+//   scint_scattered_image  Dynspec.calc_scattered_image        dynspec.py:3553-3570 (kernels: scatim.hpp)
 //
 // Everything here is HBM-bound streaming work (a gather along each delay row, column and row
 // reductions).  Compiled with -ffp-contract=off: the interpolation must round like NumPy's
@@ -301,6 +302,8 @@ block_moment_final_kernel(const double* partial, int np, double inv_n, int take_
 
 }  // namespace scint
 
+#include "scatim.hpp"
+
 using namespace scint;
 
 extern "C" int32_t scint_spline_resample(const double* dyn, int64_t nf, int64_t nt, int32_t reverse,
@@ -424,5 +427,74 @@ extern "C" int32_t scint_block_std(const double* a, int64_t ld, int64_t nc, int6
                            1.0 / (double)total, pass, pass ? out : mean);
         SCINT_LAUNCH_CHECK();
     }
+    return SCINT_OK;
+}
+
+// ------------------------------------------------------------------------------
+// scattered image
+// ------------------------------------------------------------------------------
+static size_t scat_plane_bytes(int64_t nrow, int64_t nx) { return align_up(sizeof(double) * (size_t)nrow * (size_t)nx, 256); }
+
+extern "C" int32_t scint_scattered_image_workspace_bytes(int64_t nrow, int64_t sampling, size_t* bytes) {
+    SCINT_REQUIRE(bytes && nrow >= 4 && sampling >= 1, "scattered_image_workspace_bytes: bad arguments");
+    *bytes = 3 * scat_plane_bytes(nrow, 2 * sampling + 1) + 256;      // A, the forward values, the moments; the flag
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_scattered_image(const double* sspec_db, int64_t ld, int64_t row0, int64_t row1, int64_t col0,
+                                         int64_t col1, const double* tdel, const double* row_sys, const double* row_end,
+                                         int64_t row_warm, const int32_t* row_idx, const double* row_coef,
+                                         const double* col_sys, const double* col_end, int64_t col_block_rows,
+                                         int64_t col_warm, const double* fdop_x, const double* fdop_y, double eta,
+                                         int64_t sampling, double* image, int32_t* nonfinite, void* workspace,
+                                         size_t workspace_bytes, void* stream_) {
+    SCINT_REQUIRE(sspec_db && tdel && row_sys && row_end && row_idx && row_coef && col_sys && col_end && fdop_x && fdop_y &&
+                  image && nonfinite && workspace, "scattered_image: null pointer");
+    const int64_t nrow = row1 - row0, n = col1 - col0;
+    SCINT_REQUIRE(row0 >= 0 && col0 >= 0 && col1 <= ld && nrow >= 4 && n >= 4, "scattered_image: the crop needs at least 4 x 4 pixels");
+    SCINT_REQUIRE(sampling >= 1 && sampling <= 32767, "scattered_image: bad sampling");
+    SCINT_REQUIRE(row_warm >= 0 && row_warm <= kScatMaxWarm && col_warm >= 0, "scattered_image: bad warm-up length");
+    size_t need = 0;
+    scint_scattered_image_workspace_bytes(nrow, sampling, &need);
+    if (workspace_bytes < need) { set_error("scint: scattered_image workspace too small"); return SCINT_E_WORKSPACE; }
+    hipStream_t stream = (hipStream_t)stream_;
+    const int64_t nx = 2 * sampling + 1, ny = sampling + 1;
+    Carver carve(workspace, workspace_bytes);
+    double* A = carve.take<double>((size_t)nrow * nx);
+    double* D = carve.take<double>((size_t)nrow * nx);
+    double* Mc = carve.take<double>((size_t)nrow * nx);
+    SCINT_HIP(hipMemsetAsync(nonfinite, 0, sizeof(int32_t), stream));
+    // pass A: rows.  One chunk when the interior knots fit a workgroup, else chunks with a warm-up on both sides.
+    ScatRows p;
+    p.sspec = sspec_db; p.ld = ld; p.row0 = row0; p.col0 = col0; p.nrow = nrow; p.n = n;
+    p.ih = row_sys; p.finv6 = row_sys + n; p.fbeta = row_sys + 2 * n; p.bsup = row_sys + 3 * n;
+    p.e0 = row_end[0]; p.e1 = row_end[1]; p.e2 = row_end[2]; p.e3 = row_end[3];
+    if (n - 2 <= kScatRegion) { p.valid = n - 2; p.warm = 0; }
+    else {
+        SCINT_REQUIRE(row_warm >= 1, "scattered_image: a row longer than one chunk needs a warm-up length");
+        p.warm = row_warm; p.valid = kScatRegion - 2 * row_warm - 1;
+    }
+    p.idx = row_idx; p.coef = row_coef; p.nx = nx; p.A = A; p.nonfinite = nonfinite;
+    const int64_t nchunk = ceil_div(n - 2, p.valid);
+    const int64_t ngroup = std::min<int64_t>(kScatMaxGroups, ceil_div(nrow, kScatRows));
+    hipLaunchKernelGGL(scat_rows_kernel, dim3((unsigned)nchunk, (unsigned)ngroup), dim3(256), 0, stream, p);
+    SCINT_LAUNCH_CHECK();
+    // pass B: columns of A (knots: the delay axis), lanes across the nx columns
+    SplineSys s{col_sys, col_sys + nrow, col_sys + 2 * nrow, col_sys + 3 * nrow, col_end[0], col_end[1], col_end[2], col_end[3]};
+    const int64_t rows = nrow - 2;
+    if (col_block_rows <= 0 || col_block_rows > rows) col_block_rows = rows;
+    const int64_t nblk = ceil_div(rows, col_block_rows);
+    SCINT_REQUIRE(nblk <= 65535, "scattered_image: too many delay blocks");
+    const dim3 grid((unsigned)ceil_div(nx, 64), (unsigned)nblk);
+    hipLaunchKernelGGL(spline_forward_kernel, grid, dim3(64), 0, stream, (const double*)A, nrow, nx, 0, s, col_block_rows,
+                       col_warm, D);
+    SCINT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(spline_backward_kernel, grid, dim3(64), 0, stream, (const double*)D, nrow, nx, s, col_block_rows, col_warm, Mc);
+    SCINT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(spline_ends_kernel, dim3((unsigned)ceil_div(nx, 256)), dim3(256), 0, stream, nrow, nx, s, Mc);
+    SCINT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(scat_image_kernel, dim3((unsigned)ceil_div(nx, 256), (unsigned)ny), dim3(256), 0, stream, (const double*)A,
+                       (const double*)Mc, tdel, nrow, fdop_x, fdop_y, eta, nx, ny, image);
+    SCINT_LAUNCH_CHECK();
     return SCINT_OK;
 }

@@ -14,6 +14,9 @@ reference ``Dynspec``, or plain arrays) with
   1920-2183, 970-1313): the arc-curvature search on the secondary spectrum that supplies
   ``prep_thetatheta`` with its default curvature bounds (``scintools_amd/arcfit.py``).
 
+* ``calc_scattered_image`` (dynspec.py:3412-3582): the secondary spectrum mapped through the curvature onto the sky; the
+  bicubic spline interpolation runs on the GPU (``scint_scattered_image``).
+
 Cleaning, velocity / trapezoid rescaling and plotting are out of scope.
 """
 import ctypes
@@ -247,6 +250,7 @@ class Dynspec:
 
     norm_sspec = arcfit.norm_sspec
     fit_arc = arcfit.fit_arc
+    calc_scattered_image = arcfit.calc_scattered_image
 
     @property
     def normsspec(self):
