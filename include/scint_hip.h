@@ -670,6 +670,43 @@ int32_t scint_scattered_image(const double* sspec_db, int64_t ld, int64_t row0, 
                               const double* fx, const double* fy, double eta, int64_t sampling, double* image,
                               int32_t* nonfinite, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Dynamic-spectrum cleaning: Dynspec.zap, refill, correct_dyn (dynspec.py:3856-3870, 3273-3323, 3325-3410) and
+ * ththmod.svd_model (ththmod.py:18-35).  Arrays are row-major float64 [nf][nt] without padding, on the device.
+ *
+ * scint_zap: in place.  median = np.median of the non-NaN elements (radix select on the order-preserving 64-bit key; an even
+ *   count gives (a + b) / 2 of the two middle elements; +-inf take part), mdev = the same of |x - median|; an element becomes
+ *   NaN where |x - median| / mdev > sigma.  Bit-exact: integer counting only.  stats (device, may be NULL) = {median, mdev}.
+ *   No non-NaN element: both NaN, nothing changes.  Asynchronous.  Workspace: scint_zap_workspace_bytes().
+ * scint_refill_median: out = in with every NaN replaced by the median of its kf x kt window (both odd, kf kt <= 225) of
+ *   `in with NaN -> fill`, zero padding beyond the edges (scipy.signal.medfilt); other elements are copied.  out != in.
+ * scint_refill_linear: in place.  line_valid[nf] (axis 0) or [nt] (axis 1), 1 = the line holds data: every element of a line
+ *   flagged 0 becomes slope * (i - i0) + v0, slope = (v1 - v0) / (i1 - i0), between the nearest valid lines i0 < i < i1 on
+ *   either side (np.interp's arithmetic, not contracted); without a valid line on one side it is left as it is.
+ * scint_svd_model: model = sum over the top p singular triplets of a = (a V) V^T with V [nt][p] the dominant right singular
+ *   subspace, by block iteration on a^T a from the orthonormal start v0[p][nt] (a zero row is a deflated column);
+ *   corrected = a / |model|.  Either output may be NULL.  1 <= p <= 8.  Stops when |a^T a V - V H|_F <= tol lambda_p, H = V^T a^T a V,
+ *   lambda_p its smallest eigenvalue among the columns not deflated (checked every fourth step); SCINT_E_NOCONV after max_iter
+ *   steps, SCINT_E_NONFINITE for a NaN or inf element.  status_out (device, may be NULL): 4 + 8 doubles {residual, lambda_p,
+ *   lambda_1, active columns, the eigenvalues of H descending}; *iters_out (HOST, may be NULL).  No atomics.  Synchronous.
+ *   Workspace: scint_svd_model_workspace_bytes(nf, nt).
+ * scint_nanmean_axis: np.nanmean(a, axis): axis 1 -> out[nf], axis 0 -> out[nt] (needs the workspace of
+ *   scint_nanmean_axis_workspace_bytes; fixed summation order, not NumPy's).  A line without data gives NaN.
+ * scint_divide_axis: in place, a[i][j] /= v[i] (axis 0) or v[j] (axis 1).  Both asynchronous. */
+int32_t scint_zap_workspace_bytes(size_t* bytes /*HOST*/);
+int32_t scint_zap(double* dyn, int64_t n, double sigma, double* stats, void* workspace, size_t workspace_bytes, void* stream);
+int32_t scint_refill_median(const double* in, int64_t nf, int64_t nt, int64_t kf, int64_t kt, double fill, double* out,
+                            void* stream);
+int32_t scint_refill_linear(double* dyn, int64_t nf, int64_t nt, int32_t axis, const uint8_t* line_valid, void* stream);
+int32_t scint_svd_model_workspace_bytes(int64_t nf, int64_t nt, size_t* bytes /*HOST*/);
+int32_t scint_svd_model(const double* a, int64_t nf, int64_t nt, int32_t p, const double* v0, double tol, int32_t max_iter,
+                        double* model, double* corrected, double* status_out, int32_t* iters_out /*HOST*/,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int32_t scint_nanmean_axis_workspace_bytes(int64_t nf, int64_t nt, size_t* bytes /*HOST*/);
+int32_t scint_nanmean_axis(const double* a, int64_t nf, int64_t nt, int32_t axis, double* out, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int32_t scint_divide_axis(double* a, int64_t nf, int64_t nt, int32_t axis, const double* v, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

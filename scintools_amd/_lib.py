@@ -142,6 +142,16 @@ _SIGNATURES = {
     "scint_scattered_image_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
     "scint_scattered_image": ([_P, c_int64, c_int64, c_int64, c_int64, c_int64, _P, _P, POINTER(c_double), c_int64, _P, _P, _P,
                                POINTER(c_double), c_int64, c_int64, _P, _P, c_double, c_int64, _P, _P, _P, c_size_t, _P], c_int32),
+    "scint_zap_workspace_bytes": ([POINTER(c_size_t)], c_int32),
+    "scint_zap": ([_P, c_int64, c_double, _P, _P, c_size_t, _P], c_int32),
+    "scint_refill_median": ([_P, c_int64, c_int64, c_int64, c_int64, c_double, _P, _P], c_int32),
+    "scint_refill_linear": ([_P, c_int64, c_int64, c_int32, _P, _P], c_int32),
+    "scint_svd_model_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
+    "scint_svd_model": ([_P, c_int64, c_int64, c_int32, _P, c_double, c_int32, _P, _P, _P, POINTER(c_int32), _P, c_size_t, _P],
+                        c_int32),
+    "scint_nanmean_axis_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
+    "scint_nanmean_axis": ([_P, c_int64, c_int64, c_int32, _P, _P, c_size_t, _P], c_int32),
+    "scint_divide_axis": ([_P, c_int64, c_int64, c_int32, _P, _P], c_int32),
 }
 
 _lib = None

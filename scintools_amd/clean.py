@@ -1,0 +1,368 @@
+"""Dynamic-spectrum cleaning: ``trim_edges``, ``crop_dyn``, ``zap``, ``refill``, ``correct_dyn``, ``auto_processing`` of the
+reference ``Dynspec`` (dynspec.py:259-328, 3816-3870, 3273-3410, 422-440) and ``ththmod.svd_model`` (ththmod.py:18-35).
+
+The functions are bound onto ``scintools_amd.dynspec.Dynspec`` as ``arcfit``'s are.  ``self.dyn`` stays a NumPy attribute: every
+method uploads the array once, runs the kernels of ``csrc/clean.hpp`` and downloads the result once.  What runs where:
+
+* ``zap``: both medians (an exact radix select over float64, NaN excluded) and the NaN mask on the device; bit-exact.
+* ``refill('median')``: the 2-D median filter (zero padding, only the NaN pixels) on the device; bit-exact.  The mean of the
+  valid pixels -- the fill value, and the final mean fill of every method -- is one ``np.mean`` of the host array: its bits are
+  those of NumPy's pairwise summation of the compacted pixels, which is the contract.
+* ``refill('linear')`` (and ``'biharmonic'``, which falls back to it as the reference does without scikit-image): gaps that are
+  whole channels or whole sub-integrations are interpolated across on the device; any other mask raises
+  ``NotImplementedError`` (the reference's answer then depends on Qhull's tie-breaking on the regular grid).
+* ``correct_dyn(svd=True)``: the top ``nmodes`` singular triplets by block iteration on the device, the model and the divide
+  too.  ``svd=False``: the two ``nanmean`` s and the divides on the device, ``savgol_filter`` of the two vectors on the host.
+* ``trim_edges``, ``crop_dyn``: host only.
+
+Stopping rule of the block iteration: ``|A^T A V - V H|_F <= SVD_TOL * lambda_p`` (``H = V^T A^T A V``, ``lambda_p`` its smallest
+eigenvalue), the Ritz-residual rule of the eigenvalue sweeps with ``SVD_TOL = ththmod.DEFAULT_TOL = 1e-12``.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib, device
+from .device import ptr
+
+SVD_TOL = 1e-12            # = ththmod.DEFAULT_TOL (tests/test_clean_cpu.py checks that they agree)
+SVD_MAX_ITER = 4000
+MAX_MODES = 4              # correct_dyn / svd_model; the kernels carry up to 8 columns (a complex array needs two per mode)
+MEDIAN_MAX_WINDOW = 225    # kf * kt of refill('median') (csrc/clean.hpp, kMedMaxWindow)
+
+_IRREGULAR = ("refill(method={0!r}): only gaps that are whole channels or whole sub-integrations are interpolated on the "
+              "device.  For any other mask (isolated pixels, blocks, channels and sub-integrations together) the reference's "
+              "griddata triangulates a regular grid, a degenerate Delaunay input whose answer depends on Qhull's tie-breaking; "
+              "use method='median'")
+
+
+def is_valid(array):
+    """The pixels that count as data: finite ones (NaN and +-inf are not)."""
+    return np.isfinite(array)
+
+
+def _lib_ready():
+    lib = _lib.load()
+    device.require_gpu()
+    return lib
+
+
+# ----------------------------------------------------------------------------
+# device calls on host arrays
+# ----------------------------------------------------------------------------
+def zap_device(dyn, sigma=7):
+    """(zapped copy of ``dyn``, median, mdev) of ``Dynspec.zap`` from the device (``scint_zap``)."""
+    lib = _lib_ready()
+    t = device.to_device(np.array(dyn, dtype=np.float64), torch.float64)
+    stats = device.empty((2,), torch.float64)
+    need = ctypes.c_size_t()
+    _lib.check(lib.scint_zap_workspace_bytes(ctypes.byref(need)), "zap_workspace_bytes")
+    ws = device.workspace.get(need.value)
+    _lib.check(lib.scint_zap(ptr(t), int(t.numel()), float(sigma), ptr(stats), ptr(ws), ws.numel(), device.stream_ptr()),
+               "scint_zap")
+    med, mdev = (float(v) for v in stats.cpu().numpy())
+    return t.cpu().numpy(), med, mdev
+
+
+def _kernel_size(kernel_size):
+    """(kf, kt) as scipy.signal.medfilt reads ``kernel_size`` for a 2-D array, with its error for an even size."""
+    ks = np.asarray(kernel_size)
+    if ks.shape == ():
+        ks = np.repeat(ks.item(), 2)
+    if ks.shape != (2,):
+        raise ValueError("kernel_size must be an integer or one integer per axis")
+    for k in ks:
+        if (k % 2) != 1:
+            raise ValueError("Each element of kernel_size should be odd.")
+    kf, kt = int(ks[0]), int(ks[1])
+    if kf * kt > MEDIAN_MAX_WINDOW:
+        raise ValueError(f"refill(method='median'): a window of {kf} x {kt} holds more than {MEDIAN_MAX_WINDOW} elements, "
+                         "the most the device filter selects from")
+    return kf, kt
+
+
+def median_fill_device(dyn, kf, kt, fill):
+    """``dyn`` with every NaN replaced by the median of its kf x kt window of ``dyn with NaN -> fill`` (zero padded)."""
+    lib = _lib_ready()
+    t = device.to_device(dyn, torch.float64)
+    nf, nt = (int(v) for v in t.shape)
+    out = device.empty((nf, nt), torch.float64)
+    _lib.check(lib.scint_refill_median(ptr(t), nf, nt, kf, kt, float(fill), ptr(out), device.stream_ptr()), "scint_refill_median")
+    return out.cpu().numpy()
+
+
+def linear_fill_device(dyn, axis, line_valid):
+    """A copy of ``dyn`` with the lines (axis 0: channels, axis 1: sub-integrations) flagged invalid interpolated across."""
+    lib = _lib_ready()
+    t = device.to_device(np.array(dyn, dtype=np.float64), torch.float64)
+    nf, nt = (int(v) for v in t.shape)
+    v = device.to_device(np.asarray(line_valid, dtype=np.uint8), torch.uint8)
+    _lib.check(lib.scint_refill_linear(ptr(t), nf, nt, int(axis), ptr(v), device.stream_ptr()), "scint_refill_linear")
+    return t.cpu().numpy()
+
+
+def _start_basis(nt, p):
+    """Orthonormal start of the block iteration, [p][nt]: a seeded Gaussian block whose first column leans on the constant
+    vector (a dynamic spectrum is positive); rows beyond min(nt, p) are zero (deflated from the start)."""
+    g = np.random.default_rng(20240229).standard_normal((nt, p))
+    g[:, 0] = 1.0 + 0.1 * g[:, 0]
+    q = np.linalg.qr(g)[0]
+    v0 = np.zeros((p, nt))
+    v0[:q.shape[1]] = q.T
+    return v0
+
+
+def svd_device(arr, p, want_corrected=True, info=None):
+    """(model, arr / |model|) of the real 2-D ``arr`` from its top ``p`` singular triplets (``scint_svd_model``)."""
+    lib = _lib_ready()
+    t = device.to_device(arr, torch.float64)
+    nf, nt = (int(v) for v in t.shape)
+    v0 = device.to_device(_start_basis(nt, p), torch.float64)
+    model = device.empty((nf, nt), torch.float64)
+    corrected = device.empty((nf, nt), torch.float64) if want_corrected else None
+    status = device.empty((12,), torch.float64)
+    need = ctypes.c_size_t()
+    _lib.check(lib.scint_svd_model_workspace_bytes(nf, nt, ctypes.byref(need)), "svd_model_workspace_bytes")
+    ws = device.workspace.get(need.value)
+    iters = ctypes.c_int32()
+    rc = lib.scint_svd_model(ptr(t), nf, nt, int(p), ptr(v0), SVD_TOL, SVD_MAX_ITER, ptr(model), ptr(corrected), ptr(status),
+                             ctypes.byref(iters), ptr(ws), ws.numel(), device.stream_ptr())
+    if rc == _lib.SCINT_E_NONFINITE:
+        raise ValueError("svd_model: the array holds a NaN or an infinite element (numpy.linalg.svd does not converge either)")
+    if rc == _lib.SCINT_E_NOCONV:
+        st = status.cpu().numpy()
+        raise _lib.ScintHipError(f"svd_model: the block iteration stopped after {iters.value} steps at a residual of {st[0]:.3g} "
+                                 f"(wanted {SVD_TOL:g} * {st[1]:.3g}): singular values {p} and {p + 1} are too close, or mode {p} "
+                                 "is below 3 % of the first")
+    _lib.check(rc, "scint_svd_model")
+    if info is not None:
+        st = status.cpu().numpy()
+        info.update(iters=iters.value, residual=st[0], lam_min=st[1], lam_max=st[2], active=int(st[3]), lam=st[4:4 + p].copy())
+    return model.cpu().numpy(), (corrected.cpu().numpy() if want_corrected else None)
+
+
+def _check_nmodes(nmodes):
+    if int(nmodes) != nmodes or nmodes < 0:
+        raise ValueError("nmodes must be a non-negative integer")
+    if nmodes > MAX_MODES:
+        raise ValueError(f"nmodes = {nmodes}: the device block iteration carries at most {MAX_MODES} modes")
+    return int(nmodes)
+
+
+def svd_model(arr, nmodes=1, info=None):
+    """``ththmod.svd_model`` (ththmod.py:18-35): the model of ``arr`` from its first ``nmodes`` singular triplets, complex128.
+    A complex array runs on the same real kernels through its real 2 x 2 block form (every mode then takes two columns)."""
+    arr = np.asarray(arr)
+    if arr.ndim != 2:
+        raise ValueError("svd_model needs a 2-D array")
+    nmodes = _check_nmodes(nmodes)
+    nf, nt = arr.shape
+    if nmodes == 0:
+        return np.zeros((nf, nt), np.complex128)
+    if np.iscomplexobj(arr):
+        re, im = np.ascontiguousarray(arr.real, dtype=float), np.ascontiguousarray(arr.imag, dtype=float)
+        m = svd_device(np.block([[re, -im], [im, re]]), 2 * nmodes, want_corrected=False, info=info)[0]
+        return m[:nf, :nt] + 1j * m[nf:, :nt]
+    return svd_device(np.ascontiguousarray(arr, dtype=float), nmodes, want_corrected=False, info=info)[0].astype(np.complex128)
+
+
+def nanmean_device(t, axis):
+    """np.nanmean of the device array ``t`` along ``axis`` as a host vector."""
+    lib = _lib.load()
+    nf, nt = (int(v) for v in t.shape)
+    out = device.empty((nf if axis == 1 else nt,), torch.float64)
+    need = ctypes.c_size_t()
+    _lib.check(lib.scint_nanmean_axis_workspace_bytes(nf, nt, ctypes.byref(need)), "nanmean_axis_workspace_bytes")
+    ws = device.workspace.get(max(need.value, 256))
+    _lib.check(lib.scint_nanmean_axis(ptr(t), nf, nt, int(axis), ptr(out), ptr(ws), ws.numel(), device.stream_ptr()),
+               "scint_nanmean_axis")
+    return out.cpu().numpy()
+
+
+def divide_device(t, axis, vec):
+    """t[i][j] /= vec[i] (axis 0) or vec[j] (axis 1), in place on the device."""
+    lib = _lib.load()
+    nf, nt = (int(v) for v in t.shape)
+    v = device.to_device(np.ascontiguousarray(vec, dtype=float), torch.float64)
+    _lib.check(lib.scint_divide_axis(ptr(t), nf, nt, int(axis), ptr(v), device.stream_ptr()), "scint_divide_axis")
+
+
+# ----------------------------------------------------------------------------
+# the methods
+# ----------------------------------------------------------------------------
+def zap(self, sigma=7):
+    """Basic zapping (RFI mitigation) of the dynamic spectrum (dynspec.py:3856-3870): NaN where the deviation from the median
+    exceeds ``sigma`` median deviations.  Both medians and the mask come from the device; every other pixel keeps its bits."""
+    out, _, _ = zap_device(self.dyn, sigma)
+    np.copyto(self.dyn, out)
+
+
+_NO_BIHARMONIC = 'Warning: biharmonic inpainting not available.Defaulting to linear interpolation.'   # the reference's text
+_DEFAULT_KERNEL = "Warning: kernel size is set to default."
+
+
+def _whole_line_gaps(bad):
+    """(axis, validity flag per line) when the invalid pixels form whole channels (axis 0) or whole sub-integrations (axis 1)."""
+    for axis in (0, 1):
+        dead = bad.all(axis=1 - axis)
+        if np.array_equal(bad, np.expand_dims(dead, 1 - axis) & np.ones_like(bad)):
+            return axis, ~dead
+    return None
+
+
+def refill(self, method='biharmonic', zeros=True, kernel_size=5, linear=True):
+    """Replace the NaN values (and by default the zeros) of the dynamic spectrum (dynspec.py:3273-3323); see the module text for
+    which masks ``'linear'`` accepts.  ``'biharmonic'`` falls back to ``'linear'`` with the reference's warning."""
+    if method == 'biharmonic':                          # scikit-image is never used here: the reference's fallback, always
+        print(_NO_BIHARMONIC)
+        method = 'linear'
+    if zeros:
+        np.copyto(self.dyn, np.nan, where=(self.dyn == 0))
+    if method == 'median':
+        if np.ndim(kernel_size) == 0 and kernel_size == 5:
+            print(_DEFAULT_KERNEL)
+        kf, kt = _kernel_size(kernel_size)
+        np.copyto(self.dyn, median_fill_device(self.dyn, kf, kt, np.mean(self.dyn[is_valid(self.dyn)])))
+    elif linear and method in ('linear', 'cubic', 'nearest'):
+        if method != 'linear':
+            raise NotImplementedError(_IRREGULAR.format(method) + " (and 'cubic' / 'nearest' are not built at all)")
+        bad = ~is_valid(self.dyn)                       # griddata sees the finite pixels only (np.ma.masked_invalid)
+        if bad.all():
+            raise ValueError("refill: no valid pixel to interpolate from")
+        if not bad.any():
+            self.dyn = np.array(self.dyn, dtype=np.float64)
+        else:
+            found = _whole_line_gaps(bad)
+            if found is None:
+                raise NotImplementedError(_IRREGULAR.format(method))
+            self.dyn = linear_fill_device(self.dyn, *found)
+    # every method ends with the mean of the valid pixels in whatever is still NaN (gaps at an edge, linear=False)
+    np.copyto(self.dyn, np.mean(self.dyn[is_valid(self.dyn)]), where=np.isnan(self.dyn))
+
+
+def _without_zeros(vec):
+    """The vector with its exact zeros replaced, in place, by the mean of the whole vector (the zeros included)."""
+    vec[vec == 0] = np.mean(vec)
+    return vec
+
+
+def _smoothed(vec, nsmooth):
+    if nsmooth is None:
+        return vec
+    from scipy.signal import savgol_filter
+    return savgol_filter(vec, nsmooth, 1)
+
+
+def correct_dyn(self, svd=True, nmodes=1, frequency=True, time=True, lamsteps=False, nsmooth=None, velocity=False):
+    """Correct for apparent flux variations in time and frequency (dynspec.py:3325-3410).  The reference's aliasing is kept: in
+    the plain case the working array IS ``self.dyn`` until the first divide makes a new one, so the in-place NaN -> 0, 0 -> NaN and
+    NaN -> 0 steps on ``self.dyn`` hit it too; with ``lamsteps`` they hit ``self.dyn`` alone, which nothing then reads."""
+    if velocity:
+        raise NotImplementedError("velocity scaling is outside the accelerated hot path")
+    if svd:
+        nmodes = _check_nmodes(nmodes)
+    if hasattr(self, 'svd_model'):
+        print('Warning: An svd_model exists. Check before applying twice')
+    if lamsteps and not type(self).lamdyn.present(self):
+        self.scale_dyn(lamsteps=lamsteps)
+    work = self.lamdyn if lamsteps else self.dyn
+    work[np.isnan(work)] = 0
+
+    if svd and nmodes == 0:
+        self.svd_model = np.zeros(work.shape, np.complex128)
+        work = work / np.abs(self.svd_model)
+    elif svd:
+        model, work = svd_device(np.ascontiguousarray(work, dtype=float), nmodes)
+        self.svd_model = model.astype(np.complex128)
+    else:
+        on_device = None
+        for axis, wanted in ((1, frequency), (0, time)):          # the mean over time per channel, then over frequency
+            if not wanted:
+                continue
+            self.dyn[self.dyn == 0] = np.nan            # (aliases `work` in the plain case until the first divide)
+            if on_device is None:
+                _lib_ready()
+                on_device = device.to_device(np.array(work, dtype=np.float64), torch.float64)
+            profile = _without_zeros(nanmean_device(on_device, axis))
+            if axis == 1:
+                self.bandpass = profile                 # the unsmoothed one is what the reference keeps
+            divide_device(on_device, 1 - axis, _smoothed(profile, nsmooth))
+        self.dyn[np.isnan(self.dyn)] = 0
+        if on_device is not None:
+            work = on_device.cpu().numpy()
+
+    if lamsteps:
+        self.lamdyn = work
+    else:
+        self.dyn = work
+
+
+def _edge_is_empty(line, most_zeros):
+    """One look at an edge line (a view of the array): zero it when more than ``most_zeros`` of its pixels are zero; is it all
+    zero now?"""
+    if np.count_nonzero(line == 0) > most_zeros:
+        line[...] = 0
+    return not np.any(line)
+
+
+def _rederive(self, digits, time_step):
+    """Shift the time axis to start at zero (the start goes into ``mjd``) and re-derive the sizes, the band and the centre
+    frequency, rounded to ``digits`` as the calling method of the reference rounds them."""
+    start = np.min(self.times)
+    self.mjd += start / 86400
+    self.times -= start
+    self.nchan, self.nsub = len(self.freqs), len(self.times)
+    self.bw = round(max(self.freqs) - min(self.freqs) + self.df, digits)
+    self.freq = round(np.mean(self.freqs), digits)
+    if time_step:
+        self.dt = round(np.mean(np.diff(self.times)), digits)
+        self.tobs = round(max(self.times) + self.dt, digits)
+        self.df = self.bw / self.nchan
+
+
+def trim_edges(self, bandwagon_frac=0.5, remove_short_sub=True):
+    """Find and remove the band edges (dynspec.py:259-328): NaN -> 0, then each edge line is dropped while it is all zero, an
+    edge line with more than ``bandwagon_frac`` zeros being zeroed first.  The thresholds use the array's ORIGINAL sizes on both
+    axes, as the reference's do; the attributes are re-derived with its roundings (3 digits; ``df`` becomes ``bw / nchan``).  An
+    all-zero array raises ``ValueError`` (the reference's loop runs off the end).  ``remove_short_sub`` is accepted and unused,
+    as in the reference."""
+    self.dyn[np.isnan(self.dyn)] = 0
+    nr, nc = self.dyn.shape
+    if not np.any(self.dyn):
+        raise ValueError("trim_edges: the dynamic spectrum is zero everywhere")
+    # first and last channel, then first and last sub-integration
+    for axis, at, most_zeros in ((0, 0, bandwagon_frac * nc), (0, -1, bandwagon_frac * nc),
+                                 (1, 0, bandwagon_frac * nr), (1, -1, bandwagon_frac * nr)):
+        while _edge_is_empty(self.dyn[at, :] if axis == 0 else self.dyn[:, at], most_zeros):
+            self.dyn = np.delete(self.dyn, at, axis=axis)
+            if axis == 0:
+                self.freqs = np.delete(self.freqs, at)
+            else:
+                self.times = np.delete(self.times, at)
+            if self.dyn.size == 0:
+                raise ValueError("trim_edges: every line of the dynamic spectrum was trimmed")
+    _rederive(self, 3, time_step=True)
+
+
+def crop_dyn(self, fmin=0, fmax=np.inf, tmin=0, tmax=np.inf):
+    """Crop the dynamic spectrum to fmin..fmax (MHz) and tmin..tmax (minutes) (dynspec.py:3816-3854).  ``bw`` and ``freq`` are
+    rounded to 2 digits here; ``tobs`` becomes ``tmax - tmin`` when tmax cuts the observation and ``tobs - tmin`` otherwise (both
+    in seconds, not re-derived from the kept samples); ``df`` and ``dt`` keep their values."""
+    in_band = (self.freqs >= fmin) & (self.freqs <= fmax)
+    first_s, last_s = 60 * tmin, 60 * tmax
+    in_span = (self.times >= first_s) & (self.times <= last_s)
+    self.tobs = (last_s if last_s < self.tobs else self.tobs) - first_s
+    self.dyn = self.dyn[in_band][:, in_span]
+    self.freqs, self.times = self.freqs[in_band], self.times[in_span]
+    _rederive(self, 2, time_step=False)
+
+
+def auto_processing(self, lamsteps=False, remove_short_sub=True):
+    """The reference's automatic processing (dynspec.py:422-440): its five calls, in its order."""
+    self.trim_edges(remove_short_sub=remove_short_sub)
+    self.refill()
+    self.calc_acf()
+    if lamsteps:
+        self.scale_dyn()
+    self.calc_sspec(lamsteps=lamsteps)

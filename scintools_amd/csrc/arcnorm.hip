@@ -6,6 +6,8 @@
 //   scint_row_nanmean      delay response of subtract_artefacts dynspec.py:2060-2061
 //   scint_block_std        fit_arc's noise estimate             dynspec.py:1097-1101
 //   scint_scattered_image  Dynspec.calc_scattered_image        dynspec.py:3553-3570 (kernels: scatim.hpp)
+//   scint_zap, scint_refill_median / _linear, scint_svd_model, scint_nanmean_axis, scint_divide_axis
+//                          Dynspec.zap / refill / correct_dyn   dynspec.py:3856-3870, 3273-3410 (kernels: clean.hpp)
 //
 // Everything here is HBM-bound streaming work (a gather along each delay row, column and row
 // reductions).  Compiled with -ffp-contract=off: the interpolation must round like NumPy's
@@ -303,6 +305,7 @@ block_moment_final_kernel(const double* partial, int np, double inv_n, int take_
 }  // namespace scint
 
 #include "scatim.hpp"
+#include "clean.hpp"
 
 using namespace scint;
 
@@ -495,6 +498,161 @@ extern "C" int32_t scint_scattered_image(const double* sspec_db, int64_t ld, int
     SCINT_LAUNCH_CHECK();
     hipLaunchKernelGGL(scat_image_kernel, dim3((unsigned)ceil_div(nx, 256), (unsigned)ny), dim3(256), 0, stream, (const double*)A,
                        (const double*)Mc, tdel, nrow, fdop_x, fdop_y, eta, nx, ny, image);
+    SCINT_LAUNCH_CHECK();
+    return SCINT_OK;
+}
+
+// ------------------------------------------------------------------------------
+// cleaning: zap, refill, correct_dyn (kernels: clean.hpp)
+// ------------------------------------------------------------------------------
+extern "C" int32_t scint_zap_workspace_bytes(size_t* bytes) {
+    SCINT_REQUIRE(bytes, "zap_workspace_bytes: null pointer");
+    *bytes = align_up(sizeof(ZapState), 256);
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_zap(double* dyn, int64_t n, double sigma, double* stats, void* workspace, size_t workspace_bytes,
+                             void* stream_) {
+    SCINT_REQUIRE(dyn && workspace, "zap: null pointer");
+    SCINT_REQUIRE(n >= 1, "zap: empty array");
+    if (workspace_bytes < sizeof(ZapState)) { set_error("scint: zap workspace too small"); return SCINT_E_WORKSPACE; }
+    hipStream_t stream = (hipStream_t)stream_;
+    ZapState* st = (ZapState*)workspace;
+    SCINT_HIP(hipMemsetAsync(st, 0, sizeof(ZapState), stream));
+    const int blocks = (int)std::min<int64_t>(kZapMaxBlocks, ceil_div(n, 256));
+    for (int mode = 0; mode < 2; ++mode)
+        for (int shift = 56; shift >= 0; shift -= 8) {
+            hipLaunchKernelGGL(zap_hist_kernel, dim3(blocks), dim3(256), 0, stream, (const double*)dyn, n, mode, shift, st);
+            SCINT_LAUNCH_CHECK();
+            hipLaunchKernelGGL(zap_pick_kernel, dim3(1), dim3(64), 0, stream, mode, shift, st);
+            SCINT_LAUNCH_CHECK();
+        }
+    hipLaunchKernelGGL(zap_apply_kernel, dim3(blocks), dim3(256), 0, stream, dyn, n, sigma, (const ZapState*)st);
+    SCINT_LAUNCH_CHECK();
+    if (stats) SCINT_HIP(hipMemcpyAsync(stats, st->value, 2 * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_refill_median(const double* in, int64_t nf, int64_t nt, int64_t kf, int64_t kt, double fill,
+                                       double* out, void* stream_) {
+    SCINT_REQUIRE(in && out && in != out, "refill_median: null or aliased pointer");
+    SCINT_REQUIRE(nf >= 1 && nt >= 1, "refill_median: bad sizes");
+    SCINT_REQUIRE(kf >= 1 && kt >= 1 && (kf & 1) && (kt & 1), "refill_median: each kernel size must be odd");
+    SCINT_REQUIRE(kf * kt <= kMedMaxWindow, "refill_median: the window holds more than 225 elements");
+    SCINT_REQUIRE(ceil_div(nf, kMedTile) <= 65535, "refill_median: more than 1048560 channels");
+    hipLaunchKernelGGL(refill_median_kernel, dim3((unsigned)ceil_div(nt, kMedTile), (unsigned)ceil_div(nf, kMedTile)), dim3(256),
+                       0, (hipStream_t)stream_, in, nf, nt, (int)kf, (int)kt, fill, out);
+    SCINT_LAUNCH_CHECK();
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_refill_linear(double* dyn, int64_t nf, int64_t nt, int32_t axis, const uint8_t* line_valid,
+                                       void* stream_) {
+    SCINT_REQUIRE(dyn && line_valid, "refill_linear: null pointer");
+    SCINT_REQUIRE(nf >= 1 && nt >= 1 && (axis == 0 || axis == 1), "refill_linear: bad arguments");
+    hipLaunchKernelGGL(refill_linear_kernel, dim3((unsigned)ceil_div(nt, 256), (unsigned)std::min<int64_t>(nf, 65535)), dim3(256),
+                       0, (hipStream_t)stream_, dyn, nf, nt, (int)axis, line_valid);
+    SCINT_LAUNCH_CHECK();
+    return SCINT_OK;
+}
+
+static int64_t clean_row_blocks(int64_t nf) { return std::min<int64_t>(kSvdMaxRowBlocks, ceil_div(nf, 32)); }
+
+extern "C" int32_t scint_svd_model_workspace_bytes(int64_t nf, int64_t nt, size_t* bytes) {
+    SCINT_REQUIRE(bytes && nf >= 1 && nt >= 1, "svd_model_workspace_bytes: bad arguments");
+    const size_t vec = align_up(sizeof(double) * kSvdMaxP * (size_t)nt, 256);
+    *bytes = 2 * vec + (size_t)clean_row_blocks(nf) * vec + align_up(sizeof(double) * kSvdMaxP * (size_t)nf, 256) + 512;
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_svd_model(const double* a, int64_t nf, int64_t nt, int32_t p, const double* v0, double tol,
+                                   int32_t max_iter, double* model, double* corrected, double* status_out, int32_t* iters_out,
+                                   void* workspace, size_t workspace_bytes, void* stream_) {
+    SCINT_REQUIRE(a && v0 && workspace && (model || corrected), "svd_model: null pointer");
+    SCINT_REQUIRE(nf >= 1 && nt >= 1, "svd_model: bad sizes");
+    SCINT_REQUIRE(p >= 1 && p <= kSvdMaxP, "svd_model: 1 to 8 columns");
+    SCINT_REQUIRE(tol > 0.0 && max_iter >= 1, "svd_model: bad tolerance or iteration limit");
+    size_t need = 0;
+    scint_svd_model_workspace_bytes(nf, nt, &need);
+    if (workspace_bytes < need) { set_error("scint: svd_model workspace too small"); return SCINT_E_WORKSPACE; }
+    hipStream_t stream = (hipStream_t)stream_;
+    const int64_t nblk = clean_row_blocks(nf), rows_per_block = ceil_div(nf, nblk);
+    Carver carve(workspace, workspace_bytes);
+    double* V = carve.take<double>((size_t)kSvdMaxP * nt);
+    double* Y = carve.take<double>((size_t)kSvdMaxP * nt);
+    double* part = carve.take<double>((size_t)nblk * kSvdMaxP * nt);
+    double* T = carve.take<double>((size_t)kSvdMaxP * nf);
+    SvdStatus* status = carve.take<SvdStatus>(1);
+    SCINT_HIP(hipMemcpyAsync(V, v0, sizeof(double) * (size_t)p * nt, hipMemcpyDeviceToDevice, stream));
+    const dim3 grid_av((unsigned)ceil_div(nf, 4)), grid_aty((unsigned)ceil_div(nt, 256), (unsigned)nblk);
+    SvdStatus h;
+    bool done = false;
+    int it = 0;
+    while (!done && it < max_iter) {
+        ++it;
+        hipLaunchKernelGGL(svd_av_kernel, grid_av, dim3(256), 0, stream, a, nf, nt, (const double*)V, (int)p, T);
+        SCINT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(svd_aty_kernel, grid_aty, dim3(256), 0, stream, a, nf, nt, (const double*)T, (int)p, rows_per_block, part);
+        SCINT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(svd_reduce_kernel, dim3((unsigned)ceil_div(nt, 256), (unsigned)p), dim3(256), 0, stream,
+                           (const double*)part, (int)nblk, nt, Y);
+        SCINT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(svd_step_kernel, dim3(1), dim3(256), 0, stream, nt, (int)p, V, Y, status);
+        SCINT_LAUNCH_CHECK();
+        if (it % 4 == 0 || it == max_iter) {            // the host looks at the residual every fourth step
+            SCINT_HIP(hipMemcpyAsync(&h, status, sizeof(SvdStatus), hipMemcpyDeviceToHost, stream));
+            SCINT_HIP(hipStreamSynchronize(stream));
+            if (!(h.res == h.res)) { set_error("scint: svd_model: the array is not finite"); return SCINT_E_NONFINITE; }
+            done = h.active == 0.0 || h.res <= tol * h.lam_min;
+        }
+    }
+    if (iters_out) *iters_out = it;
+    if (status_out) SCINT_HIP(hipMemcpyAsync(status_out, status, sizeof(SvdStatus), hipMemcpyDeviceToDevice, stream));
+    if (!done) { set_error("scint: svd_model: the block iteration did not reach its residual"); return SCINT_E_NOCONV; }
+    hipLaunchKernelGGL(svd_av_kernel, grid_av, dim3(256), 0, stream, a, nf, nt, (const double*)V, (int)p, T);
+    SCINT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(svd_model_kernel, dim3((unsigned)ceil_div(nt, 256), (unsigned)std::min<int64_t>(nf, 65535)), dim3(256), 0,
+                       stream, a, nf, nt, (const double*)T, (const double*)V, (int)p, model, corrected);
+    SCINT_LAUNCH_CHECK();
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_nanmean_axis_workspace_bytes(int64_t nf, int64_t nt, size_t* bytes) {
+    SCINT_REQUIRE(bytes && nf >= 1 && nt >= 1, "nanmean_axis_workspace_bytes: bad arguments");
+    *bytes = sizeof(double) * 2 * (size_t)clean_row_blocks(nf) * (size_t)nt;
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_nanmean_axis(const double* a, int64_t nf, int64_t nt, int32_t axis, double* out, void* workspace,
+                                      size_t workspace_bytes, void* stream_) {
+    SCINT_REQUIRE(a && out, "nanmean_axis: null pointer");
+    SCINT_REQUIRE(nf >= 1 && nt >= 1 && (axis == 0 || axis == 1), "nanmean_axis: bad arguments");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (axis == 1) {                                    // over time: one value per channel
+        hipLaunchKernelGGL(clean_row_nanmean_kernel, dim3((unsigned)ceil_div(nf, 4)), dim3(256), 0, stream, a, nf, nt, out);
+        SCINT_LAUNCH_CHECK();
+        return SCINT_OK;
+    }
+    size_t need = 0;
+    scint_nanmean_axis_workspace_bytes(nf, nt, &need);
+    SCINT_REQUIRE(workspace, "nanmean_axis: null workspace");
+    if (workspace_bytes < need) { set_error("scint: nanmean_axis workspace too small"); return SCINT_E_WORKSPACE; }
+    const int64_t nblk = clean_row_blocks(nf), rows_per_block = ceil_div(nf, nblk);
+    double* part = (double*)workspace;
+    hipLaunchKernelGGL(clean_col_nanmean_kernel, dim3((unsigned)ceil_div(nt, 256), (unsigned)nblk), dim3(256), 0, stream, a, nf, nt,
+                       rows_per_block, part);
+    SCINT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(clean_col_final_kernel, dim3((unsigned)ceil_div(nt, 256)), dim3(256), 0, stream, (const double*)part,
+                       (int)nblk, nt, out);
+    SCINT_LAUNCH_CHECK();
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_divide_axis(double* a, int64_t nf, int64_t nt, int32_t axis, const double* v, void* stream_) {
+    SCINT_REQUIRE(a && v, "divide_axis: null pointer");
+    SCINT_REQUIRE(nf >= 1 && nt >= 1 && (axis == 0 || axis == 1), "divide_axis: bad arguments");
+    hipLaunchKernelGGL(clean_divide_kernel, dim3((unsigned)ceil_div(nt, 256), (unsigned)std::min<int64_t>(nf, 65535)), dim3(256), 0,
+                       (hipStream_t)stream_, a, nf, nt, (int)axis, v);
     SCINT_LAUNCH_CHECK();
     return SCINT_OK;
 }

@@ -17,7 +17,11 @@ reference ``Dynspec``, or plain arrays) with
 * ``calc_scattered_image`` (dynspec.py:3412-3582): the secondary spectrum mapped through the curvature onto the sky; the
   bicubic spline interpolation runs on the GPU (``scint_scattered_image``).
 
-Cleaning, velocity / trapezoid rescaling and plotting are out of scope.
+* ``trim_edges``, ``crop_dyn``, ``zap``, ``refill``, ``correct_dyn``, ``auto_processing`` (dynspec.py:259-328, 3816-3870,
+  3273-3410, 422-440): the cleaning chain; medians, the median filter, gap interpolation and the truncated SVD run on the GPU
+  (``scintools_amd/clean.py``).
+
+Velocity / trapezoid rescaling, ``cut_dyn`` and plotting are out of scope.
 """
 import ctypes
 import functools
@@ -28,7 +32,7 @@ import numpy as np
 import scipy.constants as sc
 import torch
 
-from . import _lib, arcfit, psrflux, units
+from . import _lib, arcfit, clean, psrflux, units
 from . import ththmod as thth
 from .device import DeviceBacked, empty, ptr, require_gpu, stream_ptr, to_device, workspace
 
@@ -178,8 +182,9 @@ class Dynspec:
         self.dyn = np.asarray(dyn.dyn, dtype=float)
         self.nchan = int(getattr(dyn, "nchan", self.dyn.shape[0]))
         self.nsub = int(getattr(dyn, "nsub", self.dyn.shape[1]))
-        self.df = float(getattr(dyn, "df", np.abs(self.freqs[1] - self.freqs[0])))
-        self.dt = float(getattr(dyn, "dt", self.times[1] - self.times[0]))
+        # (the defaults are formed only when the attribute is missing: a single channel or sub-integration has no spacing)
+        self.df = float(dyn.df if hasattr(dyn, "df") else np.abs(self.freqs[1] - self.freqs[0]))
+        self.dt = float(dyn.dt if hasattr(dyn, "dt") else self.times[1] - self.times[0])
         self.bw = float(getattr(dyn, "bw", np.ptp(self.freqs) + self.df))
         self.freq = float(getattr(dyn, "freq", np.mean(self.freqs)))
         tobs = getattr(dyn, "tobs", None)
@@ -251,6 +256,13 @@ class Dynspec:
     norm_sspec = arcfit.norm_sspec
     fit_arc = arcfit.fit_arc
     calc_scattered_image = arcfit.calc_scattered_image
+
+    trim_edges = clean.trim_edges
+    crop_dyn = clean.crop_dyn
+    zap = clean.zap
+    refill = clean.refill
+    correct_dyn = clean.correct_dyn
+    auto_processing = clean.auto_processing
 
     @property
     def normsspec(self):

@@ -50,6 +50,7 @@ from scipy.optimize import curve_fit, minimize
 
 from . import _lib, units
 from . import device as _dv
+from .clean import svd_model  # noqa: F401  (ththmod.py:18-35, on the kernels of correct_dyn: csrc/clean.hpp)
 from .device import empty, ptr, require_gpu, stream_ptr, workspace
 
 DEFAULT_TOL = 1e-12       # Ritz-residual tolerance of the Lanczos eigen-solver
