@@ -195,8 +195,10 @@ def test_device_crop_tables_equal_the_host_ones(emu, case):
 
 @pytest.mark.parametrize("size", [192, 300])
 def test_eigenvalue_sweep_several_block_rows(emu, to, size):
-    """Matrices of 3 and 5 block rows: pairs of rows per mat-vec workgroup with strips beyond the first column
-    range, a second row that starts one tile late, an unpaired last row (the `case` fixture stays below 128)."""
+    """Matrices of 3 and 5 block rows (the `case` fixture stays below 128): one row group of eight block rows per mat-vec
+    workgroup, here a single short group of 3 or 5 rows -- strips of one tile at 3 block rows, of two at 5, cut on the
+    first row's column grid, so that row I + r starts r tiles late and has nothing in the strips left of its diagonal.
+    (Full and several row groups, every strip length: tests/test_sweep_classes_emu_cpu.py.)"""
     from scintools_amd.synth import arc_dynspec
     dyn, freqs, times, eta_true = arc_dynspec(size, size, seed=9, nimg=6, noise=0.05)
     dyn = dyn - dyn.mean()
@@ -244,8 +246,9 @@ def _sweep_stats(thth):
 
 @pytest.mark.parametrize("size", [96, 192, 300, 520])
 def test_mixed_sweep_against_float64_sweep_and_arpack(emu, to, size):
-    """Mixed precision (eigen_packed.hip): the passes stream complex64 tiles -- four block rows per workgroup, rows that
-    start one to three tiles late, a last group of one to three rows, strips of two and four tiles --, the returned
+    """Mixed precision (eigen_packed.hip): the passes stream complex64 tiles -- eight block rows per workgroup (kRows32),
+    rows that start one to seven tiles late; 2, 3 and 5 block rows are one short group with strips of one and two tiles,
+    9 block rows (size 520) a full group of three four-tile strips and a last group of one row --, the returned
     value is the Ritz value of the certificate pass on the complex128 tiles.  It has to agree with the float64 sweep far
     inside its tolerance (both are Ritz values of the SAME float64 matrix under the same bound) and with ARPACK to the
     parity bar; every curvature goes through exactly one certificate, which here passes at its first step."""
