@@ -707,6 +707,24 @@ int32_t scint_nanmean_axis(const double* a, int64_t nf, int64_t nt, int32_t axis
                            size_t workspace_bytes, void* stream);
 int32_t scint_divide_axis(double* a, int64_t nf, int64_t nt, int32_t axis, const double* v, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Scaled-time (NuT) conjugate spectrum: scint_utils.slow_FT (scint_utils.py:655-703).  dyn[nt][nf] is [time][frequency], row-major
+ * float64 on the device; fscale[nf] = freqs / fref (device; formed by the caller as the reference does, lines 683-686).
+ *   S1[k][j] = sum_t dyn[t][j] exp(-2 pi i (t fscale[j]) ft[k]),  ft = np.fft.fftfreq(nt, 1)              (lines 688-694)
+ *   out = fftshift(fft(fftshift(S1, axes=0), axis=1), axes=1)                                             (lines 695-700)
+ * (line 695 as the reference means it: it spells the keyword `axis`, which NumPy rejects).  out[nt][nf] complex128.
+ * The [nt][nt][nf] array of the reference is never formed: per (k, j) the exponentials are the product of two tables of 64 and
+ * nt / 64 entries, each entry from its own float64 phase reduced modulo one cycle (no recurrence).  The frequency transform is the
+ * row FFT when nf is a power of two in [16, 8192] and a direct sum with exactly reduced twiddle indices otherwise (nt nf^2 terms).
+ * Non-finite input propagates as in NumPy (one NaN pixel makes every output NaN); there is no input scan.  No atomics: equal
+ * inputs give equal bits.  Asynchronous on `stream`.
+ * Limits: 1 <= nt, nf <= 2^20 and ceil(nt / 64) * 64 * nf <= 2^30 (SCINT_E_ARG otherwise): every index is formed in 64 bits,
+ *   the launch grids stay below 65536 in y, and the integer k t of a phase stays exact in float64.
+ * Workspace: scint_slow_ft_workspace_bytes(nt, nf): the zero-padded transpose of dyn and S1, about 24 nt nf bytes. */
+int32_t scint_slow_ft_workspace_bytes(int64_t nt, int64_t nf, size_t* bytes /*HOST*/);
+int32_t scint_slow_ft(const double* dyn /*[nt][nf]*/, int64_t nt, int64_t nf, const double* fscale /*[nf] device*/,
+                      scint_c128* out /*[nt][nf]*/, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -152,6 +152,8 @@ _SIGNATURES = {
     "scint_nanmean_axis_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
     "scint_nanmean_axis": ([_P, c_int64, c_int64, c_int32, _P, _P, c_size_t, _P], c_int32),
     "scint_divide_axis": ([_P, c_int64, c_int64, c_int32, _P, _P], c_int32),
+    "scint_slow_ft_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
+    "scint_slow_ft": ([_P, c_int64, c_int64, _P, _P, _P, c_size_t, _P], c_int32),
 }
 
 _lib = None

@@ -5,6 +5,7 @@
 //   scint_model_from_recov  ifft2(ifftshift(recov)).real  (ththmod.py:322-324), complex-to-real
 //   scint_mean / scint_chisq  small deterministic reductions
 //   scint_sim_*             the split-step screen simulator (scint_sim.py), functors in sim.hpp
+//   scint_slow_ft           the scaled-time (NuT) conjugate spectrum (scint_utils.slow_FT), kernels in slowft.hpp
 //
 // Every transform is "source -> row FFT -> column FFT -> sink":
 //   RowSource  produces element (row, j) of the padded real/complex input (this is where
@@ -34,6 +35,7 @@
 #include "packed.hpp"
 #include "prof.hpp"
 #include "sim.hpp"
+#include "slowft.hpp"
 #include "sspec.hpp"
 
 namespace scint {
@@ -1997,4 +1999,52 @@ extern "C" int32_t scint_sim_pulse(const void* spe, int64_t nx, int64_t nf, cons
     SCINT_REQUIRE(nf >= 8 && nf <= 4096 && is_pow2(nf), "sim_pulse: 2 nf must be a power of two in [16, 8192]");
     return launch_fft_rows(2 * nf, nx, SimPulseLoad{(const float*)spe, window, (int)nf},
                            SimPulseStore{out, (int)nf, nx * 2 * nf}, (hipStream_t)stream_);
+}
+
+// ------------------------------------------------------------------------------
+// scint_slow_ft: the scaled-time (NuT) conjugate spectrum, scint_utils.slow_FT (kernels: slowft.hpp)
+// ------------------------------------------------------------------------------
+namespace scint {
+static int64_t slow_ft_padded(int64_t nt) { return ceil_div(nt, kSlowB) * kSlowB; }
+static int32_t slow_ft_check_shape(int64_t nt, int64_t nf) {
+    SCINT_REQUIRE(nt >= 1 && nf >= 1, "slow_ft: bad shape (nt and nf must be at least 1)");
+    // grid.y of the transpose (nf / 32) and of the direct sum (nf / 256) stay below 65536; k' t stays exact in float64
+    SCINT_REQUIRE(nt <= (1 << 20) && nf <= (1 << 20), "slow_ft: nt and nf must not exceed 2^20");
+    SCINT_REQUIRE(slow_ft_padded(nt) * nf <= ((int64_t)1 << 30), "slow_ft: nt (rounded up to 64) * nf must not exceed 2^30");
+    return SCINT_OK;
+}
+}  // namespace scint
+
+extern "C" int32_t scint_slow_ft_workspace_bytes(int64_t nt, int64_t nf, size_t* bytes) {
+    SCINT_REQUIRE(bytes != nullptr, "slow_ft_workspace_bytes: null output");
+    const int32_t rc = slow_ft_check_shape(nt, nf);
+    if (rc != SCINT_OK) return rc;
+    *bytes = align_up(sizeof(double) * (size_t)(slow_ft_padded(nt) * nf), 256) + sizeof(cplx) * (size_t)(nt * nf) + 256;
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_slow_ft(const double* dyn, int64_t nt, int64_t nf, const double* fscale, scint_c128* out_,
+                                 void* workspace, size_t workspace_bytes, void* stream_) {
+    SCINT_REQUIRE(dyn && fscale && out_ && workspace, "slow_ft: null pointer");
+    int32_t rc = slow_ft_check_shape(nt, nf);
+    if (rc != SCINT_OK) return rc;
+    const int64_t ntp = slow_ft_padded(nt);
+    Carver cv(workspace, workspace_bytes);
+    double* dynT = cv.take<double>((size_t)(ntp * nf));
+    cplx* s1 = cv.take<cplx>((size_t)(nt * nf));
+    if (!cv.ok()) { set_error("scint: slow_ft workspace too small"); return SCINT_E_WORKSPACE; }
+    hipStream_t stream = (hipStream_t)stream_;
+    cplx* out = (cplx*)out_;
+    hipLaunchKernelGGL(slowft_transpose_kernel, dim3((unsigned)(ntp / 32), (unsigned)ceil_div(nf, 32)), dim3(256), 0, stream,
+                       dyn, nt, nf, ntp, dynT);
+    hipLaunchKernelGGL(slowft_stage1_kernel, dim3((unsigned)nf, (unsigned)ceil_div(nt / 2 + 1, kSlowThreads)), dim3(kSlowThreads),
+                       0, stream, dynT, fscale, s1, nt, ntp, nf, 1.0 / (double)nt);
+    SCINT_LAUNCH_CHECK();
+    if (is_pow2(nf) && nf >= 16 && nf <= 8192)
+        return launch_fft_rows(nf, nt, SimRowLoad{s1, (int)nf}, SlowShiftStore{out, (int)nf}, stream);
+    const cplx* tw = twiddle_table(nf);
+    if (!tw) return SCINT_E_HIP;
+    hipLaunchKernelGGL(slowft_dft_kernel, dim3((unsigned)nt, (unsigned)ceil_div(nf, 256)), dim3(256), 0, stream, s1, tw, out, nf);
+    SCINT_LAUNCH_CHECK();
+    return SCINT_OK;
 }
