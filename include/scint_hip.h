@@ -8,7 +8,7 @@
  * /root/reference/scintools).  INTEGRATION.md shows that binding.
  *
  * Conventions
- *   - every pointer is a DEVICE pointer owned by the caller unless marked HOST;
+ *   - every pointer is a DEVICE pointer owned by the caller unless marked SCINT_HOST;
  *   - arrays are C-contiguous; complex data is interleaved (re, im) float64,
  *     i.e. numpy complex128 / HIP double2;
  *   - sizes are int64_t, flags int32_t, the return value is an int32_t status:
@@ -39,6 +39,24 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+
+/* Marks a pointer parameter that is read or written by the CPU during the call; every other pointer is device memory.
+ * (Empty for the compiler; the Python binding derives its argument types from these prototypes: scintools_amd/_lib.py.) */
+#define SCINT_HOST
+
+/* The version of the argument lists below, returned by scint_version(): an argument added in the middle of a list shifts every
+ * pointer after it, so a binding refuses a library of another version.  An entry point may be ADDED without a new version.
+ *   101: scint_profile_end takes the length of the caller's arrays;
+ *   102: scint_sweep_workgroups;
+ *   103: scint_chisq_sweep takes crop_group;
+ *   104: calc_sspec through persistent kernels (no signature change; the version binds library and package: _lib.load checks it);
+ *   105: scint_mosaic_* / scint_chunk_cut;
+ *   106: scint_retrieval_tail takes class_id (one-row back-map, pair counts per class);
+ *   107: the rank-1 Hermitian back-map on a uniform theta grid is rev_diag_kernel (scint_rev_map leaves which kernel ran in word 9
+ *        of its workspace; SCINT_REV_DIAG=0 keeps the general kernel);
+ *   108: scint_two_curve_map / scint_sv_sweep_multi (the thin-screen search, scint_thin_geom);
+ *   (the VLBI entry points -- scint_cs_complex_batch / scint_vlbi_composite / scint_eigh_top_batch -- only ADD symbols: no bump) */
+#define SCINT_ABI_VERSION 108
 
 #define SCINT_OK 0
 #define SCINT_E_ARG 1        /* bad size / null pointer / unsupported option   */
@@ -76,7 +94,7 @@ typedef struct {
 /* ---- diagnostics -------------------------------------------------------- */
 int32_t scint_version(void);
 /* HOST buffer; copies the calling thread's last error text. */
-int32_t scint_last_error(char* buf, size_t n);
+int32_t scint_last_error(char* SCINT_HOST buf, size_t n);
 /* Number of visible HIP devices (0 if none): lets the wrapper fail loudly. */
 int32_t scint_device_count(void);
 
@@ -93,8 +111,8 @@ int32_t scint_device_count(void);
  * three kernels of the two-trip scint_sspec (input copy + sums, strided axis, row transforms with
  * |.|^2 / dB).  Not thread-safe; off by default. */
 int32_t scint_profile_begin(void);
-int32_t scint_profile_end(double* ms_out /*HOST[count]*/, double* ms_sum_out /*HOST[count]*/,
-                          int64_t* launches_out /*HOST[count]*/, int32_t count);
+int32_t scint_profile_end(double* SCINT_HOST ms_out /*[count]*/, double* SCINT_HOST ms_sum_out /*[count]*/,
+                          int64_t* SCINT_HOST launches_out /*[count]*/, int32_t count);
 
 /* ---- secondary spectrum: Dynspec.calc_sspec core (dynspec.py:3665-3721) -- */
 /* dyn[nf,nt] -> sec[(halve? nrfft/2 : nrfft), ncfft] in dB, where
@@ -102,7 +120,7 @@ int32_t scint_profile_end(double* ms_out /*HOST[count]*/, double* ms_sum_out /*H
  * win_t[nt], win_f[nf]: tapers of scint_utils.get_window (:810-832) or NULL.
  * pd_fd[ncfft], pd_td[nrfft/2]: post-darkening sin^2 vectors (dynspec.py:3706-3711),
  * required iff prewhite.  Workspace: scint_sspec_workspace_bytes(). */
-int32_t scint_sspec_workspace_bytes(int64_t nf, int64_t nt, size_t* bytes /*HOST*/);
+int32_t scint_sspec_workspace_bytes(int64_t nf, int64_t nt, size_t* SCINT_HOST bytes);
 int32_t scint_sspec(const double* dyn, int64_t nf, int64_t nt,
                     const double* win_t, const double* win_f,
                     int32_t prewhite, int32_t halve,
@@ -116,19 +134,19 @@ int32_t scint_sspec(const double* dyn, int64_t nf, int64_t nt,
  * If `incoherent` != 0 the output is abs(CS) + 0j (ththmod.py:801).
  * cs_out[(npad+1)*nf, (npad+1)*nt].  Any sizes (non powers of two go through a
  * chirp-z pass).  Workspace: scint_cs_workspace_bytes(). */
-int32_t scint_cs_workspace_bytes(int64_t nf, int64_t nt, int64_t npad, size_t* bytes /*HOST*/);
+int32_t scint_cs_workspace_bytes(int64_t nf, int64_t nt, int64_t npad, size_t* SCINT_HOST bytes);
 int32_t scint_cs(const double* dspec, int64_t nf, int64_t nt, int64_t npad,
                  double pad_value, int64_t mask_lo, int64_t mask_hi, int32_t incoherent,
                  scint_c128* cs_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* mean of a device array (np.mean of the chunk), synchronous, HOST result. */
-int32_t scint_mean(const double* x, int64_t n, double* mean_out /*HOST*/, void* stream);
+int32_t scint_mean(const double* x, int64_t n, double* SCINT_HOST mean_out, void* stream);
 
 /* ---- CS -> theta-theta: thth_map + thth_redmap (ththmod.py:56-173) ------- */
 /* th_cents[M]: bin centres (ththmod.py:83-84).  keep_idx[N]: indices (into
  * th_cents, ascending) of the centres kept by the crop (:153-155); pass the
  * identity for plain thth_map.  thth_out[N,N].  hermitian: ththmod.py:108-114. */
-int32_t scint_thth_map(const scint_c128* cs, const scint_cs_geom* geom /*HOST*/,
+int32_t scint_thth_map(const scint_c128* cs, const scint_cs_geom* SCINT_HOST geom,
                        const double* th_cents, int64_t M,
                        const int32_t* keep_idx, int64_t N,
                        double eta, int32_t hermitian,
@@ -148,7 +166,7 @@ int32_t scint_thth_map(const scint_c128* cs, const scint_cs_geom* geom /*HOST*/,
  * streams from a host-side scheduler that reads convergence flags back, and returns with all of them drained -- results
  * are complete (in device memory) on return, and an asynchronous fault of any queued kernel is reported by this call. */
 int32_t scint_eval_sweep_workspace_bytes(int64_t M, int64_t neta, int64_t batch,
-                                         int32_t max_iter, size_t* bytes /*HOST*/);
+                                         int32_t max_iter, size_t* SCINT_HOST bytes);
 /* Operand precision of the ITERATION of the eigenvalue sweeps (scint_eval_sweep, scint_eval_sweep_multi), per process:
  *   0  float64 throughout (the default): every Lanczos pass streams the complex128 tiles;
  *   1  mixed: the passes stream a complex64 copy of theta-theta (float64 vectors and sums), and the eigenvalue that
@@ -175,7 +193,7 @@ int32_t scint_sweep_schedule(int32_t depth, int32_t check_every, int32_t groups)
 /* Diagnostics of the calling thread's last sweep (any of the sweep entry points), for the roofline accounting:
  * out[0] algorithmic bytes of its complex64 passes (4 n (n + 1) each), out[1] of its complex128 passes (8 n (n + 1)),
  * out[2] curvatures that went through a certificate, out[3] complex128 passes those certificates took. */
-int32_t scint_sweep_stats(double* out /*HOST[4]*/);
+int32_t scint_sweep_stats(double* SCINT_HOST out /*[4]*/);
 /* Mat-vec workgroups ONE theta-theta matrix of `nb` 64-row blocks contributes to a launch of the sweep (`complex64` != 0: of the
  * complex64 kernel of the mixed sweep) -- block rows per workgroup and column tiles per strip are build constants of the library
  * (csrc/packed.hpp).  For callers that size the `batch` argument of the sweeps: resident curvatures x this = workgroups per
@@ -194,10 +212,10 @@ int32_t scint_sweep_workgroups(int32_t nb, int32_t complex64);
 /* Limits common to every sweep entry point below (eval / eigvec / chisq, single and _multi): a conjugate spectrum must hold
  * fewer than 2^31 elements (ntau * nfd; the packed gather indexes it with 32 bits) -- SCINT_E_ARG otherwise, before anything
  * is queued.  scint_thth_map / scint_rev_map / scint_modeler index with 64 bits and have no such limit. */
-int32_t scint_eval_sweep(const scint_c128* cs, const scint_cs_geom* geom /*HOST*/,
+int32_t scint_eval_sweep(const scint_c128* cs, const scint_cs_geom* SCINT_HOST geom,
                          const double* th_cents, int64_t M,
-                         const int32_t* keep_idx, const int32_t* keep_n /*HOST*/,
-                         const double* etas /*HOST*/, int64_t neta,
+                         const int32_t* keep_idx, const int32_t* SCINT_HOST keep_n,
+                         const double* SCINT_HOST etas, int64_t neta,
                          double tol, int32_t max_iter, int64_t batch,
                          double* eigs_out, int32_t* status_out, int32_t* iters_out,
                          void* workspace, size_t workspace_bytes, void* stream);
@@ -208,12 +226,12 @@ int32_t scint_eval_sweep(const scint_c128* cs, const scint_cs_geom* geom /*HOST*
  * between spectra; geoms[ncs] (HOST); th_stack[ncs][M]; curvature e reads spectrum
  * cs_index[e] (HOST) and keeps keep_idx[e*M ..] of th_stack[cs_index[e]]. */
 int32_t scint_eval_sweep_multi_workspace_bytes(int64_t M, int64_t neta, int64_t batch,
-                                               int32_t max_iter, int64_t ncs, size_t* bytes /*HOST*/);
+                                               int32_t max_iter, int64_t ncs, size_t* SCINT_HOST bytes);
 int32_t scint_eval_sweep_multi(const scint_c128* cs_stack, int64_t ncs, int64_t cs_stride,
-                               const int32_t* cs_index /*HOST*/, const scint_cs_geom* geoms /*HOST*/,
+                               const int32_t* SCINT_HOST cs_index, const scint_cs_geom* SCINT_HOST geoms,
                                const double* th_stack, int64_t M,
-                               const int32_t* keep_idx, const int32_t* keep_n /*HOST*/,
-                               const double* etas /*HOST*/, int64_t neta,
+                               const int32_t* keep_idx, const int32_t* SCINT_HOST keep_n,
+                               const double* SCINT_HOST etas, int64_t neta,
                                double tol, int32_t max_iter, int64_t batch,
                                double* eigs_out, int32_t* status_out, int32_t* iters_out,
                                void* workspace, size_t workspace_bytes, void* stream);
@@ -222,11 +240,11 @@ int32_t scint_eval_sweep_multi(const scint_c128* cs_stack, int64_t ncs, int64_t 
  * eigsh call of modeler (ththmod.py:308) for a whole curvature sweep.  vec_out[neta, vec_stride]
  * (vec_stride >= M; row i holds keep_n[i] entries).  Stops on the Ritz residual (tol). */
 int32_t scint_eigvec_sweep_workspace_bytes(int64_t M, int64_t neta, int64_t batch,
-                                           int32_t max_iter, size_t* bytes /*HOST*/);
-int32_t scint_eigvec_sweep(const scint_c128* cs, const scint_cs_geom* geom /*HOST*/,
+                                           int32_t max_iter, size_t* SCINT_HOST bytes);
+int32_t scint_eigvec_sweep(const scint_c128* cs, const scint_cs_geom* SCINT_HOST geom,
                            const double* th_cents, int64_t M,
-                           const int32_t* keep_idx, const int32_t* keep_n /*HOST*/,
-                           const double* etas /*HOST*/, int64_t neta,
+                           const int32_t* keep_idx, const int32_t* SCINT_HOST keep_n,
+                           const double* SCINT_HOST etas, int64_t neta,
                            double tol, int32_t max_iter, int64_t batch,
                            double* w_out, scint_c128* vec_out, int64_t vec_stride,
                            int32_t* status_out, int32_t* iters_out,
@@ -236,19 +254,19 @@ int32_t scint_eigvec_sweep(const scint_c128* cs, const scint_cs_geom* geom /*HOS
  * keep_idx[e*M ..] = ascending indices i with th_cents[i]^2 * etas[e] < tau_max and |th_cents[i]| < fd_half
  * (NumPy's expression, same roundings), keep_n[e] their count -- the tables the sweeps take.  th_cents,
  * keep_idx, keep_n: DEVICE; etas: HOST.  Asynchronous. */
-int32_t scint_sweep_keep(const double* th_cents, int64_t M, const double* etas /*HOST*/, int64_t neta,
+int32_t scint_sweep_keep(const double* th_cents, int64_t M, const double* SCINT_HOST etas, int64_t neta,
                          double tau_max, double fd_half, int32_t* keep_idx, int32_t* keep_n, void* stream);
 
 /* The same for MANY conjugate spectra of one shape in one batched sweep (arguments as
  * scint_eval_sweep_multi): the eigenpairs of all chunks of Dynspec.thetatheta_chunks -- one
  * modeler() call per chunk in the reference, dynspec.py:1765-1826 / ththmod.py:1455 -- in ONE call. */
 int32_t scint_eigvec_sweep_multi_workspace_bytes(int64_t M, int64_t neta, int64_t batch,
-                                                 int32_t max_iter, int64_t ncs, size_t* bytes /*HOST*/);
+                                                 int32_t max_iter, int64_t ncs, size_t* SCINT_HOST bytes);
 int32_t scint_eigvec_sweep_multi(const scint_c128* cs_stack, int64_t ncs, int64_t cs_stride,
-                                 const int32_t* cs_index /*HOST*/, const scint_cs_geom* geoms /*HOST*/,
+                                 const int32_t* SCINT_HOST cs_index, const scint_cs_geom* SCINT_HOST geoms,
                                  const double* th_stack, int64_t M,
-                                 const int32_t* keep_idx, const int32_t* keep_n /*HOST*/,
-                                 const double* etas /*HOST*/, int64_t neta,
+                                 const int32_t* keep_idx, const int32_t* SCINT_HOST keep_n,
+                                 const double* SCINT_HOST etas, int64_t neta,
                                  double tol, int32_t max_iter, int64_t batch,
                                  double* w_out, scint_c128* vec_out, int64_t vec_stride,
                                  int32_t* status_out, int32_t* iters_out,
@@ -258,7 +276,7 @@ int32_t scint_eigvec_sweep_multi(const scint_c128* cs_stack, int64_t ncs, int64_
 /* a[n,n] row-major.  v0[n] start vector or NULL (then a fixed pseudo-random
  * start, as modeler's eigsh call has no v0, ththmod.py:308).  w_out[1],
  * vec_out[n] (unit 2-norm) device outputs; status_out[1], iters_out[1]. */
-int32_t scint_eigh_top_workspace_bytes(int64_t n, int32_t max_iter, size_t* bytes /*HOST*/);
+int32_t scint_eigh_top_workspace_bytes(int64_t n, int32_t max_iter, size_t* SCINT_HOST bytes);
 int32_t scint_eigh_top(const scint_c128* a, int64_t n, const scint_c128* v0,
                        double tol, int32_t max_iter,
                        double* w_out, scint_c128* vec_out,
@@ -270,9 +288,9 @@ int32_t scint_eigh_top(const scint_c128* a, int64_t n, const scint_c128* v0,
  * vec_out[njobs][vec_stride] (row j holds n[j] entries, the rest is left as it was), status_out[njobs], iters_out[njobs]: device.
  * n, start_row: HOST.  A job with n[j] < 2 gets SCINT_E_EMPTY.  A job's arithmetic does not depend on which jobs share the call.
  * Synchronous (the done flags are read back every few steps, as in scint_eigh_top).  njobs <= 65535. */
-int32_t scint_eigh_top_batch_workspace_bytes(int64_t nmax, int32_t max_iter, int64_t njobs, size_t* bytes /*HOST*/);
-int32_t scint_eigh_top_batch(const scint_c128* a_stack, int64_t a_stride, const int32_t* n /*HOST*/,
-                             const int32_t* start_row /*HOST or NULL*/, int64_t njobs, double tol, int32_t max_iter,
+int32_t scint_eigh_top_batch_workspace_bytes(int64_t nmax, int32_t max_iter, int64_t njobs, size_t* SCINT_HOST bytes);
+int32_t scint_eigh_top_batch(const scint_c128* a_stack, int64_t a_stride, const int32_t* SCINT_HOST n,
+                             const int32_t* SCINT_HOST start_row /*or NULL*/, int64_t njobs, double tol, int32_t max_iter,
                              double* w_out, scint_c128* vec_out, int64_t vec_stride,
                              int32_t* status_out, int32_t* iters_out,
                              void* workspace, size_t workspace_bytes, void* stream);
@@ -292,17 +310,17 @@ int32_t scint_eigh_top_batch(const scint_c128* a_stack, int64_t a_stride, const 
  * pixels, each pixel within its rounding of the split sums').  After the call word 9 (uint64) of the workspace is 1 if that
  * kernel formed the image, 0 if the general one did.  Environment: SCINT_REV_DIAG=0 keeps every image (also the chi^2 sweep's)
  * on the general kernel. */
-int32_t scint_rev_map_workspace_bytes(size_t* bytes /*HOST*/);
+int32_t scint_rev_map_workspace_bytes(size_t* SCINT_HOST bytes);
 int32_t scint_rev_map(const scint_c128* thth, const scint_c128* vec, const double* w,
                       int32_t rank1, const double* th_cents, int64_t N,
-                      const scint_cs_geom* geom /*HOST*/, double eta, int32_t hermitian,
+                      const scint_cs_geom* SCINT_HOST geom, double eta, int32_t hermitian,
                       scint_c128* recov_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- model dynamic spectrum: ifft2(ifftshift(recov)).real (ththmod.py:322-324) ----------
  * recov[ntau, nfd] -> model_out[ntau, nfd].  Computed as a complex-to-real transform of the
  * Hermitian part of ifftshift(recov) when both lengths are powers of two (nfd in 32..8192): an
  * identity for any input, equal to the complex transform's real part up to rounding. */
-int32_t scint_model_workspace_bytes(int64_t ntau, int64_t nfd, size_t* bytes /*HOST*/);
+int32_t scint_model_workspace_bytes(int64_t ntau, int64_t nfd, size_t* SCINT_HOST bytes);
 int32_t scint_model_from_recov(const scint_c128* recov, int64_t ntau, int64_t nfd,
                                double* model_out, void* workspace, size_t workspace_bytes,
                                void* stream);
@@ -333,13 +351,13 @@ int32_t scint_ifft2_shifted(const scint_c128* in, int64_t rows, int64_t cols, do
  * colmajor: the host array is Fortran-ordered (numpy.copy keeps the order, NumPy's sums then walk a window column by column);
  * `dyn` itself is row-major here either way.
  * Workspace for both: scint_mosaic_workspace_bytes(cwf, cwt, nchunk) (nchunk = count for scint_mosaic_phase). */
-int32_t scint_mosaic_workspace_bytes(int64_t cwf, int64_t cwt, int64_t nchunk, size_t* bytes /*HOST*/);
+int32_t scint_mosaic_workspace_bytes(int64_t cwf, int64_t cwt, int64_t nchunk, size_t* SCINT_HOST bytes);
 int32_t scint_mosaic_phase(const scint_c128* E, int64_t ldE, const scint_c128* chunks, int64_t cwf, int64_t cwt,
                            const int64_t* jobs, int64_t count, const double* rows, const double* cols, int32_t numpy_fused,
                            void* workspace, size_t workspace_bytes, double* sums_out, void* stream);
 int32_t scint_mosaic_add(scint_c128* E, int64_t ldE, const scint_c128* chunks, int64_t cwf, int64_t cwt,
                          const int64_t* jobs, int64_t count, const double* rows, const double* cols, int32_t numpy_fused,
-                         const double* phases /*HOST*/, void* stream);
+                         const double* SCINT_HOST phases, void* stream);
 int32_t scint_chunk_cut(const double* dyn, int64_t nf, int64_t nt, const int32_t* r0, const int32_t* c0, int64_t nchunk,
                         int64_t cwf, int64_t cwt, int32_t colmajor, double* chunks_out, double* pad_out, void* workspace,
                         size_t workspace_bytes, void* stream);
@@ -359,7 +377,7 @@ int32_t scint_chunk_cut(const double* dyn, int64_t nf, int64_t nt, const int32_t
  * (parameters: phases of chunks 1 .. n - 1, then the n amplitudes); numpy.sum, so a NaN or zero of dspec / noise shows in the
  * entries it touches; zero outside the neighbour band; exactly symmetric (where the reference writes an entry from the visits
  * (N, M) and (M, N), the later one's value, as there). */
-int32_t scint_mosaic_fit_workspace_bytes(int64_t ncf, int64_t nct, int64_t cwf, int64_t cwt, size_t* bytes /*HOST*/);
+int32_t scint_mosaic_fit_workspace_bytes(int64_t ncf, int64_t nct, int64_t cwf, int64_t cwt, size_t* SCINT_HOST bytes);
 int32_t scint_mosaic_fit_eval(const scint_c128* chunks, int64_t ncf, int64_t nct, int64_t cwf, int64_t cwt, const double* rows,
                               const double* cols, const double* coef, int32_t full, int32_t numpy_fused, const double* dspec,
                               const double* noise, scint_c128* W, int32_t want, double* out, void* workspace,
@@ -379,12 +397,12 @@ int32_t scint_mosaic_fit_hess(const scint_c128* chunks, int64_t ncf, int64_t nct
  * and those counts are formed once per CLASS -- class_id (HOST [n]): consecutive chunks with equal ids share theta grid, curvature
  * and axes (the chunks of one frequency row of an observation).  rows [n][M] complex, th_red [n][M], out [n][nf][nt]: device;
  * keep_n, class_id, geoms, etas: HOST. */
-int32_t scint_cs_batch(const double* dstack, int64_t n, int64_t nf, int64_t nt, int64_t npad, const double* pads /*HOST*/,
-                       const int64_t* mask_lohi /*HOST*/, int32_t incoherent, scint_c128* cs_stack, void* workspace,
+int32_t scint_cs_batch(const double* dstack, int64_t n, int64_t nf, int64_t nt, int64_t npad, const double* SCINT_HOST pads,
+                       const int64_t* SCINT_HOST mask_lohi, int32_t incoherent, scint_c128* cs_stack, void* workspace,
                        size_t workspace_bytes, void* stream);
-int32_t scint_retrieval_tail_workspace_bytes(int64_t M, int64_t ntau, int64_t nfd, size_t* bytes /*HOST*/);
-int32_t scint_retrieval_tail(const scint_c128* rows, const double* th_red, const int32_t* keep_n /*HOST*/, const int32_t* class_id /*HOST*/,
-                             const scint_cs_geom* geoms /*HOST*/, const double* etas /*HOST*/, int64_t n, int64_t M, int64_t nf, int64_t nt,
+int32_t scint_retrieval_tail_workspace_bytes(int64_t M, int64_t ntau, int64_t nfd, size_t* SCINT_HOST bytes);
+int32_t scint_retrieval_tail(const scint_c128* rows, const double* th_red, const int32_t* SCINT_HOST keep_n, const int32_t* SCINT_HOST class_id,
+                             const scint_cs_geom* SCINT_HOST geoms, const double* SCINT_HOST etas, int64_t n, int64_t M, int64_t nf, int64_t nt,
                              double scale, scint_c128* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- multi-station (VLBI) phase retrieval: VLBI_chunk_retrieval (ththmod.py:1223-1387), a group of chunks per call
@@ -404,12 +422,12 @@ int32_t scint_retrieval_tail(const scint_c128* rows, const double* th_red, const
  *   Workspace: scint_vlbi_composite_workspace_bytes().  Synchronous.
  * The dominant eigenpair of the composites: scint_eigh_top_batch; the wavefields: scint_retrieval_tail with n_dish rows per chunk. */
 int32_t scint_cs_complex_batch(const scint_c128* xstack, int64_t n, int64_t nf, int64_t nt, int64_t npad,
-                               const int64_t* mask_lohi /*HOST*/, scint_c128* cs_stack, void* workspace,
+                               const int64_t* SCINT_HOST mask_lohi, scint_c128* cs_stack, void* workspace,
                                size_t workspace_bytes, void* stream);
-int32_t scint_vlbi_composite_workspace_bytes(int64_t nchunk, int64_t n_dish, size_t* bytes /*HOST*/);
-int32_t scint_vlbi_composite(const scint_c128* cs_stack, int64_t cs_stride, const int64_t* cs_slot /*HOST*/,
-                             const scint_cs_geom* geoms /*HOST*/, const double* th_stack, int64_t M,
-                             const int32_t* keep_idx, const int32_t* keep_n /*HOST*/, const double* etas /*HOST*/,
+int32_t scint_vlbi_composite_workspace_bytes(int64_t nchunk, int64_t n_dish, size_t* SCINT_HOST bytes);
+int32_t scint_vlbi_composite(const scint_c128* cs_stack, int64_t cs_stride, const int64_t* SCINT_HOST cs_slot,
+                             const scint_cs_geom* SCINT_HOST geoms, const double* th_stack, int64_t M,
+                             const int32_t* keep_idx, const int32_t* SCINT_HOST keep_n, const double* SCINT_HOST etas,
                              int64_t nchunk, int64_t n_dish, scint_c128* comp_out, int64_t comp_stride,
                              void* workspace, size_t workspace_bytes, void* stream);
 
@@ -417,7 +435,7 @@ int32_t scint_vlbi_composite(const scint_c128* cs_stack, int64_t cs_stride, cons
  * wavefield[rows, cols] in place.  Per iteration: fft2, zero the natural-order delay rows
  * zero_lo <= k < zero_hi (the tau < 0 half), ifft2, then where pos != 0 replace the amplitude
  * by amp (= sqrt(dyn)) keeping the phase.  Workspace: scint_gs_workspace_bytes(). */
-int32_t scint_gs_workspace_bytes(int64_t rows, int64_t cols, size_t* bytes /*HOST*/);
+int32_t scint_gs_workspace_bytes(int64_t rows, int64_t cols, size_t* SCINT_HOST bytes);
 int32_t scint_gerchberg_saxton(scint_c128* wavefield, int64_t rows, int64_t cols,
                                const double* amp, const uint8_t* pos,
                                int64_t zero_lo, int64_t zero_hi, int32_t niter,
@@ -427,7 +445,7 @@ int32_t scint_gerchberg_saxton(scint_c128* wavefield, int64_t rows, int64_t cols
  * acf_out[2nf, 2nt] = real(fftshift(ifft2(|fft2(dyn - mean, s=[2nf, 2nt])|^2))), / max if
  * normalise; the mean is subtracted only if subtract_mean (the reference skips it for
  * input_dyn).  dyn must be finite (the reference takes the mean of the valid pixels only). */
-int32_t scint_acf_workspace_bytes(int64_t nf, int64_t nt, size_t* bytes /*HOST*/);
+int32_t scint_acf_workspace_bytes(int64_t nf, int64_t nt, size_t* SCINT_HOST bytes);
 int32_t scint_acf(const double* dyn, int64_t nf, int64_t nt, int32_t subtract_mean, int32_t normalise,
                   double* acf_out, void* workspace, size_t workspace_bytes, void* stream);
 
@@ -471,14 +489,14 @@ int32_t scint_chisq(const double* model, int64_t ld_model, const double* dspec,
  * again from a written image before the call returns.  SCINT_CHISQ_FUSE=0 (environment) keeps every image written.
  * scint_chisq_sweep_last_route: of the LAST scint_chisq_sweep of the process -- fused = 1 if it took chi^2 from the accumulators,
  * redone = the curvatures it did again (tests, bench.py). */
-int32_t scint_chisq_sweep_last_route(int32_t* fused /*HOST*/, int64_t* redone /*HOST*/);
+int32_t scint_chisq_sweep_last_route(int32_t* SCINT_HOST fused, int64_t* SCINT_HOST redone);
 int32_t scint_chisq_sweep_workspace_bytes(int64_t M, int64_t neta, int64_t batch, int32_t max_iter,
                                           int64_t ntau, int64_t nfd, int64_t nf, int64_t nt,
-                                          size_t* bytes /*HOST*/);
-int32_t scint_chisq_sweep(const scint_c128* cs, const scint_cs_geom* geom /*HOST*/, const double* th_cents,
-                          int64_t M, const int32_t* keep_idx, const int32_t* keep_n /*HOST*/,
-                          const double* etas /*HOST*/, int64_t neta, double tol, int32_t max_iter,
-                          int64_t batch, const double* th_red, const int32_t* crop_group /*HOST[neta] or NULL*/,
+                                          size_t* SCINT_HOST bytes);
+int32_t scint_chisq_sweep(const scint_c128* cs, const scint_cs_geom* SCINT_HOST geom, const double* th_cents,
+                          int64_t M, const int32_t* keep_idx, const int32_t* SCINT_HOST keep_n,
+                          const double* SCINT_HOST etas, int64_t neta, double tol, int32_t max_iter,
+                          int64_t batch, const double* th_red, const int32_t* SCINT_HOST crop_group /*[neta] or NULL*/,
                           const double* dspec, int64_t nf, int64_t nt,
                           const uint8_t* mask, double noise_n, double* chisq_out, double* w_out,
                           scint_c128* vec_out, int64_t vec_stride, int32_t* status_out, int32_t* iters_out,
@@ -504,7 +522,7 @@ int32_t scint_chisq_sweep(const scint_c128* cs, const scint_cs_geom* geom /*HOST
  * workspace: 2*nf*nt doubles. */
 int32_t scint_spline_resample(const double* dyn, int64_t nf, int64_t nt, int32_t reverse,
                               const double* h, const double* sub, const double* inv,
-                              const double* sup, const double* end /*HOST [4]*/,
+                              const double* sup, const double* SCINT_HOST end /*[4]*/,
                               int64_t block_rows, int64_t warm,
                               const int32_t* idx, const double* coef, int64_t nout,
                               double* out, void* workspace, size_t workspace_bytes, void* stream);
@@ -530,7 +548,7 @@ int32_t scint_norm_sspec(const double* sspec, int64_t ld, int64_t nc, const doub
  * avg_out[k] = sum_r w[r]*norm[r,k] / sum_r w[r] over rows with rowsel[r] != 0 (NULL = all) and
  * mask[r,k] == 0.  A column with no entry gets empty_out[k] = 1 and avg_out[k] = 0 (the value
  * numpy.ma leaves under the mask).  Fixed summation order (deterministic). */
-int32_t scint_masked_colavg_workspace_bytes(int64_t nr, int64_t nx, size_t* bytes /*HOST*/);
+int32_t scint_masked_colavg_workspace_bytes(int64_t nr, int64_t nx, size_t* SCINT_HOST bytes);
 int32_t scint_masked_colavg(const double* norm, const uint8_t* mask, int64_t nr, int64_t nx,
                             const double* weights, const uint8_t* rowsel, double* avg_out,
                             uint8_t* empty_out, void* workspace, size_t workspace_bytes, void* stream);
@@ -548,7 +566,7 @@ int32_t scint_block_std(const double* a, int64_t ld, int64_t nc, int64_t r0, int
 
 /* ---- plain 2-D complex FFT (forward, numpy sign convention) -------------- */
 /* Exposed for tests: out may alias in. */
-int32_t scint_fft2_workspace_bytes(int64_t rows, int64_t cols, size_t* bytes /*HOST*/);
+int32_t scint_fft2_workspace_bytes(int64_t rows, int64_t cols, size_t* SCINT_HOST bytes);
 int32_t scint_fft2(const scint_c128* in, scint_c128* out, int64_t rows, int64_t cols,
                    void* workspace, size_t workspace_bytes, void* stream);
 
@@ -572,15 +590,15 @@ int32_t scint_fft2(const scint_c128* in, scint_c128* out, int64_t rows, int64_t 
  *   groups it ran (tests).
  * scint_sim_pulse: get_pulse's pulsewin before its transpose, out[nx][2 nf] = roll(|fft(spe * window, 2 nf)|^2, nf)
  *   (the roll of the flattened array, as np.roll without an axis); 2 nf a power of two in [16, 8192]. */
-int32_t scint_sim_screen_workspace_bytes(int64_t nx, int64_t ny, size_t* bytes /*HOST*/);
+int32_t scint_sim_screen_workspace_bytes(int64_t nx, int64_t ny, size_t* SCINT_HOST bytes);
 int32_t scint_sim_screen(const double* z1, const double* z2, int64_t nx, int64_t ny, double dqx, double dqy,
                          double a, double b, double c, double con, double alf, double inner2, double* w,
                          double* xyp, void* workspace, size_t workspace_bytes, void* stream);
-int32_t scint_sim_field_workspace_bytes(int64_t nx, int64_t ny, int64_t group, size_t* bytes /*HOST*/);
+int32_t scint_sim_field_workspace_bytes(int64_t nx, int64_t ny, int64_t group, size_t* SCINT_HOST bytes);
 int32_t scint_sim_field(const double* xyp, int64_t nx, int64_t ny, const double* scale, int64_t nf, int64_t f0,
                         int64_t f1, double ffconx, double ffcony, void* spe, float* spi, double* xyi,
                         void* workspace, size_t workspace_bytes, void* stream);
-int32_t scint_sim_last_route(int32_t* column /*HOST*/, int64_t* groups /*HOST*/);
+int32_t scint_sim_last_route(int32_t* SCINT_HOST column, int64_t* SCINT_HOST groups);
 int32_t scint_sim_pulse(const void* spe, int64_t nx, int64_t nf, const double* window, double* out, void* stream);
 
 /* ---- theoretical 2-D ACF model: scint_sim.ACF (scint_sim.py:417-766; Rickett et al. 2014, Appendix A) ---------------------
@@ -600,7 +618,7 @@ int32_t scint_sim_pulse(const void* spe, int64_t nx, int64_t nf, const double* w
  *   nsn <= 64 * 65535, ndnun <= 65536).  Five launches (four when ndnun == 2); no atomics: results are bit-reproducible.
  *   Asynchronous on `stream`.  Workspace: scint_acf_model_workspace_bytes(m, m2, nsn, ndnun) -- the phase tables
  *   (32 nsnp (m2 + (ndnun - 2) m) bytes, nsnp = nsn rounded up to 16) and one partial per (lag, block of 64 rows, s). */
-int32_t scint_acf_model_workspace_bytes(int64_t m, int64_t m2, int64_t nsn, int64_t ndnun, size_t* bytes /*HOST*/);
+int32_t scint_acf_model_workspace_bytes(int64_t m, int64_t m2, int64_t nsn, int64_t ndnun, size_t* SCINT_HOST bytes);
 int32_t scint_acf_model(const double* snp, int64_t m, const double* snp2, int64_t m2, const double* snx,
                         const double* sny, int64_t nsn, const double* dnun, int64_t ndnun, double sigxn, double sigyn,
                         double sqrtar, double alph2, double step, double step2, double* gammes, scint_c128* gamma,
@@ -630,19 +648,19 @@ int32_t scint_acf_model(const double* snp, int64_t m, const double* snp2, int64_
  *   Outputs (device): sv_out[neta] (NaN unless status 0), status_out[neta]: 0, SCINT_E_NOCONV, SCINT_E_EMPTY (no kept row or
  *   column), SCINT_E_NONFINITE, or SCINT_E_ARG = NumPy would raise IndexError in two_curve_map; iters_out[neta] Lanczos steps.
  *   At most 16384 theta1 centres.  Synchronous.  Workspace: scint_sv_sweep_multi_workspace_bytes(). */
-int32_t scint_two_curve_map_workspace_bytes(size_t* bytes /*HOST*/);
-int32_t scint_two_curve_map(const scint_c128* cs, const scint_thin_geom* geom /*HOST*/,
+int32_t scint_two_curve_map_workspace_bytes(size_t* SCINT_HOST bytes);
+int32_t scint_two_curve_map(const scint_c128* cs, const scint_thin_geom* SCINT_HOST geom,
                             const double* th1, int64_t M1, const double* th2, int64_t M2,
-                            double eta1, double eta2, const int32_t* ranges /*HOST[6]*/, int32_t check,
+                            double eta1, double eta2, const int32_t* SCINT_HOST ranges /*[6]*/, int32_t check,
                             scint_c128* thth_out, int32_t* raise_out, void* workspace, size_t workspace_bytes,
                             void* stream);
 int32_t scint_sv_sweep_multi_workspace_bytes(int64_t M1, int64_t M2, int64_t neta, int64_t batch, int32_t max_iter,
-                                             int64_t ncs, size_t* bytes /*HOST*/);
+                                             int64_t ncs, size_t* SCINT_HOST bytes);
 int32_t scint_sv_sweep_multi(const scint_c128* cs_stack, int64_t ncs, int64_t cs_stride,
-                             const int32_t* cs_index /*HOST*/, const scint_thin_geom* geoms /*HOST*/,
+                             const int32_t* SCINT_HOST cs_index, const scint_thin_geom* SCINT_HOST geoms,
                              const double* th1_stack, int64_t M1, const double* th2_stack, int64_t M2,
-                             const int32_t* ranges /*HOST[neta][6]*/, const int32_t* check /*HOST*/,
-                             const double* etas1 /*HOST*/, const double* etas2 /*HOST*/, int64_t neta,
+                             const int32_t* SCINT_HOST ranges /*[neta][6]*/, const int32_t* SCINT_HOST check,
+                             const double* SCINT_HOST etas1, const double* SCINT_HOST etas2, int64_t neta,
                              double tol, int32_t max_iter, int64_t batch,
                              double* sv_out, int32_t* status_out, int32_t* iters_out,
                              void* workspace, size_t workspace_bytes, void* stream);
@@ -662,11 +680,11 @@ int32_t scint_sv_sweep_multi(const scint_c128* cs_stack, int64_t ncs, int64_t cs
  * Outputs (device): image[nx][nx]; *nonfinite = 1 if some 10**(v/10) of the crop is NaN or inf (scipy then returns NaN everywhere),
  *   else 0.  No atomics: equal inputs give equal bits.  Asynchronous on `stream`.
  * Workspace: scint_scattered_image_workspace_bytes(nrow, sampling): three nrow x nx planes. */
-int32_t scint_scattered_image_workspace_bytes(int64_t nrow, int64_t sampling, size_t* bytes /*HOST*/);
+int32_t scint_scattered_image_workspace_bytes(int64_t nrow, int64_t sampling, size_t* SCINT_HOST bytes);
 int32_t scint_scattered_image(const double* sspec_db, int64_t ld, int64_t row0, int64_t row1, int64_t col0, int64_t col1,
-                              const double* tdel, const double* row_sys, const double* row_end /*HOST[4]*/, int64_t row_warm,
+                              const double* tdel, const double* row_sys, const double* SCINT_HOST row_end /*[4]*/, int64_t row_warm,
                               const int32_t* row_idx, const double* row_coef, const double* col_sys,
-                              const double* col_end /*HOST[4]*/, int64_t col_block_rows, int64_t col_warm,
+                              const double* SCINT_HOST col_end /*[4]*/, int64_t col_block_rows, int64_t col_warm,
                               const double* fx, const double* fy, double eta, int64_t sampling, double* image,
                               int32_t* nonfinite, void* workspace, size_t workspace_bytes, void* stream);
 
@@ -693,16 +711,16 @@ int32_t scint_scattered_image(const double* sspec_db, int64_t ld, int64_t row0, 
  * scint_nanmean_axis: np.nanmean(a, axis): axis 1 -> out[nf], axis 0 -> out[nt] (needs the workspace of
  *   scint_nanmean_axis_workspace_bytes; fixed summation order, not NumPy's).  A line without data gives NaN.
  * scint_divide_axis: in place, a[i][j] /= v[i] (axis 0) or v[j] (axis 1).  Both asynchronous. */
-int32_t scint_zap_workspace_bytes(size_t* bytes /*HOST*/);
+int32_t scint_zap_workspace_bytes(size_t* SCINT_HOST bytes);
 int32_t scint_zap(double* dyn, int64_t n, double sigma, double* stats, void* workspace, size_t workspace_bytes, void* stream);
 int32_t scint_refill_median(const double* in, int64_t nf, int64_t nt, int64_t kf, int64_t kt, double fill, double* out,
                             void* stream);
 int32_t scint_refill_linear(double* dyn, int64_t nf, int64_t nt, int32_t axis, const uint8_t* line_valid, void* stream);
-int32_t scint_svd_model_workspace_bytes(int64_t nf, int64_t nt, size_t* bytes /*HOST*/);
+int32_t scint_svd_model_workspace_bytes(int64_t nf, int64_t nt, size_t* SCINT_HOST bytes);
 int32_t scint_svd_model(const double* a, int64_t nf, int64_t nt, int32_t p, const double* v0, double tol, int32_t max_iter,
-                        double* model, double* corrected, double* status_out, int32_t* iters_out /*HOST*/,
+                        double* model, double* corrected, double* status_out, int32_t* SCINT_HOST iters_out,
                         void* workspace, size_t workspace_bytes, void* stream);
-int32_t scint_nanmean_axis_workspace_bytes(int64_t nf, int64_t nt, size_t* bytes /*HOST*/);
+int32_t scint_nanmean_axis_workspace_bytes(int64_t nf, int64_t nt, size_t* SCINT_HOST bytes);
 int32_t scint_nanmean_axis(const double* a, int64_t nf, int64_t nt, int32_t axis, double* out, void* workspace,
                            size_t workspace_bytes, void* stream);
 int32_t scint_divide_axis(double* a, int64_t nf, int64_t nt, int32_t axis, const double* v, void* stream);
@@ -721,7 +739,7 @@ int32_t scint_divide_axis(double* a, int64_t nf, int64_t nt, int32_t axis, const
  * Limits: 1 <= nt, nf <= 2^20 and ceil(nt / 64) * 64 * nf <= 2^30 (SCINT_E_ARG otherwise): every index is formed in 64 bits,
  *   the launch grids stay below 65536 in y, and the integer k t of a phase stays exact in float64.
  * Workspace: scint_slow_ft_workspace_bytes(nt, nf): the zero-padded transpose of dyn and S1, about 24 nt nf bytes. */
-int32_t scint_slow_ft_workspace_bytes(int64_t nt, int64_t nf, size_t* bytes /*HOST*/);
+int32_t scint_slow_ft_workspace_bytes(int64_t nt, int64_t nf, size_t* SCINT_HOST bytes);
 int32_t scint_slow_ft(const double* dyn /*[nt][nf]*/, int64_t nt, int64_t nf, const double* fscale /*[nf] device*/,
                       scint_c128* out /*[nt][nf]*/, void* workspace, size_t workspace_bytes, void* stream);
 

@@ -5,10 +5,14 @@ entry point raises.  Loading the library itself needs only the HIP runtime, so
 ``symbols()`` works in a GPU-less container (the CPU test-suite checks that the
 library exports everything the header declares).
 """
+import collections
 import ctypes
+import operator
 import os
 import re
 from ctypes import POINTER, c_char_p, c_double, c_int32, c_int64, c_size_t, c_void_p
+
+import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libscint_hip.so")
@@ -23,6 +27,7 @@ SCINT_E_NONFINITE = 6
 
 class ScintHipError(RuntimeError):
     """A call into libscint_hip.so failed (message from scint_last_error)."""
+    status = None      # the SCINT_E_* code, where a call returned one
 
 
 class CsGeom(ctypes.Structure):
@@ -41,131 +46,170 @@ class ThinGeom(ctypes.Structure):
                 ("fd1", c_double), ("dfd", c_double)]
 
 
-_P = c_void_p  # device pointers travel as integers
-_SIGNATURES = {
-    "scint_version": ([], c_int32),
-    "scint_last_error": ([c_char_p, c_size_t], c_int32),
-    "scint_device_count": ([], c_int32),
-    "scint_profile_begin": ([], c_int32),
-    "scint_profile_end": ([POINTER(c_double), POINTER(c_double), POINTER(c_int64), c_int32], c_int32),
-    "scint_sspec_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
-    "scint_sspec": ([_P, c_int64, c_int64, _P, _P, c_int32, c_int32, _P, _P, _P, _P, c_size_t, _P], c_int32),
-    "scint_cs_workspace_bytes": ([c_int64, c_int64, c_int64, POINTER(c_size_t)], c_int32),
-    "scint_cs": ([_P, c_int64, c_int64, c_int64, c_double, c_int64, c_int64, c_int32, _P, _P, c_size_t, _P], c_int32),
-    "scint_mean": ([_P, c_int64, POINTER(c_double), _P], c_int32),
-    "scint_thth_map": ([_P, POINTER(CsGeom), _P, c_int64, _P, c_int64, c_double, c_int32, _P, _P], c_int32),
-    "scint_sweep_precision": ([c_int32], c_int32),
-    "scint_sweep_schedule": ([c_int32, c_int32, c_int32], c_int32),
-    "scint_sweep_stats": ([POINTER(c_double)], c_int32),
-    "scint_sweep_workgroups": ([c_int32, c_int32], c_int32),
-    "scint_eval_sweep_workspace_bytes": ([c_int64, c_int64, c_int64, c_int32, POINTER(c_size_t)], c_int32),
-    "scint_eval_sweep": ([_P, POINTER(CsGeom), _P, c_int64, _P, POINTER(c_int32), POINTER(c_double), c_int64,
-                          c_double, c_int32, c_int64, _P, _P, _P, _P, c_size_t, _P], c_int32),
-    "scint_eval_sweep_multi_workspace_bytes": ([c_int64, c_int64, c_int64, c_int32, c_int64, POINTER(c_size_t)],
-                                               c_int32),
-    "scint_eval_sweep_multi": ([_P, c_int64, c_int64, POINTER(c_int32), POINTER(CsGeom), _P, c_int64, _P,
-                                POINTER(c_int32), POINTER(c_double), c_int64, c_double, c_int32, c_int64,
-                                _P, _P, _P, _P, c_size_t, _P], c_int32),
-    "scint_eigvec_sweep_workspace_bytes": ([c_int64, c_int64, c_int64, c_int32, POINTER(c_size_t)], c_int32),
-    "scint_eigvec_sweep": ([_P, POINTER(CsGeom), _P, c_int64, _P, POINTER(c_int32), POINTER(c_double), c_int64,
-                            c_double, c_int32, c_int64, _P, _P, c_int64, _P, _P, _P, c_size_t, _P], c_int32),
-    "scint_sweep_keep": ([_P, c_int64, POINTER(c_double), c_int64, c_double, c_double, _P, _P, _P], c_int32),
-    "scint_eigvec_sweep_multi_workspace_bytes": ([c_int64, c_int64, c_int64, c_int32, c_int64, POINTER(c_size_t)],
-                                                 c_int32),
-    "scint_eigvec_sweep_multi": ([_P, c_int64, c_int64, POINTER(c_int32), POINTER(CsGeom), _P, c_int64, _P,
-                                  POINTER(c_int32), POINTER(c_double), c_int64, c_double, c_int32, c_int64,
-                                  _P, _P, c_int64, _P, _P, _P, c_size_t, _P], c_int32),
-    "scint_chisq_sweep_workspace_bytes": ([c_int64, c_int64, c_int64, c_int32, c_int64, c_int64, c_int64, c_int64,
-                                           POINTER(c_size_t)], c_int32),
-    "scint_chisq_sweep": ([_P, POINTER(CsGeom), _P, c_int64, _P, POINTER(c_int32), POINTER(c_double), c_int64,
-                           c_double, c_int32, c_int64, _P, POINTER(c_int32), _P, c_int64, c_int64, _P, c_double, _P, _P, _P, c_int64,
-                           _P, _P, _P, c_size_t, _P], c_int32),
-    "scint_chisq_sweep_last_route": ([POINTER(c_int32), POINTER(c_int64)], c_int32),
-    "scint_eigh_top_workspace_bytes": ([c_int64, c_int32, POINTER(c_size_t)], c_int32),
-    "scint_eigh_top": ([_P, c_int64, _P, c_double, c_int32, _P, _P, _P, _P, _P, c_size_t, _P], c_int32),
-    "scint_rev_map_workspace_bytes": ([POINTER(c_size_t)], c_int32),
-    "scint_rev_map": ([_P, _P, _P, c_int32, _P, c_int64, POINTER(CsGeom), c_double, c_int32, _P, _P, c_size_t, _P],
-                      c_int32),
-    "scint_model_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
-    "scint_model_from_recov": ([_P, c_int64, c_int64, _P, _P, c_size_t, _P], c_int32),
-    "scint_ifft2_shifted": ([_P, c_int64, c_int64, c_double, c_int64, c_int64, _P, _P, c_size_t, _P], c_int32),
-    "scint_mosaic_workspace_bytes": ([c_int64, c_int64, c_int64, POINTER(c_size_t)], c_int32),
-    "scint_mosaic_phase": ([_P, c_int64, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int32, _P, c_size_t, _P, _P], c_int32),
-    "scint_mosaic_add": ([_P, c_int64, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int32, POINTER(c_double), _P], c_int32),
-    "scint_chunk_cut": ([_P, c_int64, c_int64, _P, _P, c_int64, c_int64, c_int64, c_int32, _P, _P, _P, c_size_t, _P], c_int32),
-    "scint_mosaic_fit_workspace_bytes": ([c_int64, c_int64, c_int64, c_int64, POINTER(c_size_t)], c_int32),
-    "scint_mosaic_fit_eval": ([_P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, c_int32, c_int32, _P, _P, _P, c_int32, _P, _P, c_size_t, _P], c_int32),
-    "scint_mosaic_fit_hess": ([_P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P], c_int32),
-    "scint_cs_batch": ([_P, c_int64, c_int64, c_int64, c_int64, POINTER(c_double), POINTER(c_int64), c_int32, _P, _P, c_size_t, _P], c_int32),
-    "scint_cs_complex_batch": ([_P, c_int64, c_int64, c_int64, c_int64, POINTER(c_int64), _P, _P, c_size_t, _P], c_int32),
-    "scint_vlbi_composite_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
-    "scint_vlbi_composite": ([_P, c_int64, POINTER(c_int64), POINTER(CsGeom), _P, c_int64, _P, POINTER(c_int32), POINTER(c_double),
-                              c_int64, c_int64, _P, c_int64, _P, c_size_t, _P], c_int32),
-    "scint_eigh_top_batch_workspace_bytes": ([c_int64, c_int32, c_int64, POINTER(c_size_t)], c_int32),
-    "scint_eigh_top_batch": ([_P, c_int64, POINTER(c_int32), POINTER(c_int32), c_int64, c_double, c_int32, _P, _P, c_int64, _P, _P,
-                              _P, c_size_t, _P], c_int32),
-    "scint_retrieval_tail_workspace_bytes": ([c_int64, c_int64, c_int64, POINTER(c_size_t)], c_int32),
-    "scint_retrieval_tail": ([_P, _P, POINTER(c_int32), POINTER(c_int32), POINTER(CsGeom), POINTER(c_double), c_int64, c_int64, c_int64, c_int64,
-                              c_double, _P, _P, c_size_t, _P], c_int32),
-    "scint_gs_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
-    "scint_gerchberg_saxton": ([_P, c_int64, c_int64, _P, _P, c_int64, c_int64, c_int32, _P, c_size_t, _P], c_int32),
-    "scint_acf_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
-    "scint_acf": ([_P, c_int64, c_int64, c_int32, c_int32, _P, _P, c_size_t, _P], c_int32),
-    "scint_chisq": ([_P, c_int64, _P, c_int64, c_int64, _P, c_double, _P, _P], c_int32),
-    "scint_spline_resample": ([_P, c_int64, c_int64, c_int32, _P, _P, _P, _P, POINTER(c_double), c_int64, c_int64,
-                               _P, _P, c_int64, _P, _P, c_size_t, _P], c_int32),
-    "scint_norm_sspec": ([_P, c_int64, c_int64, _P, _P, c_int64, c_int64, c_double, c_double, c_int64, c_int64,
-                          _P, _P, _P, c_int64, _P, _P, _P, _P], c_int32),
-    "scint_masked_colavg_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
-    "scint_masked_colavg": ([_P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, c_size_t, _P], c_int32),
-    "scint_row_nanmean": ([_P, c_int64, c_int64, c_int64, c_int64, _P, c_int64, c_int64, _P, _P], c_int32),
-    "scint_block_std": ([_P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, _P, _P, c_size_t, _P], c_int32),
-    "scint_fft2_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
-    "scint_two_curve_map_workspace_bytes": ([POINTER(c_size_t)], c_int32),
-    "scint_two_curve_map": ([_P, POINTER(ThinGeom), _P, c_int64, _P, c_int64, c_double, c_double, POINTER(c_int32), c_int32,
-                             _P, _P, _P, c_size_t, _P], c_int32),
-    "scint_sv_sweep_multi_workspace_bytes": ([c_int64, c_int64, c_int64, c_int64, c_int32, c_int64, POINTER(c_size_t)], c_int32),
-    "scint_sv_sweep_multi": ([_P, c_int64, c_int64, POINTER(c_int32), POINTER(ThinGeom), _P, c_int64, _P, c_int64,
-                              POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double), c_int64,
-                              c_double, c_int32, c_int64, _P, _P, _P, _P, c_size_t, _P], c_int32),
-    "scint_fft2": ([_P, _P, c_int64, c_int64, _P, c_size_t, _P], c_int32),
-    "scint_sim_screen_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
-    "scint_sim_screen": ([_P, _P, c_int64, c_int64, c_double, c_double, c_double, c_double, c_double, c_double, c_double, c_double,
-                          _P, _P, _P, c_size_t, _P], c_int32),
-    "scint_sim_field_workspace_bytes": ([c_int64, c_int64, c_int64, POINTER(c_size_t)], c_int32),
-    "scint_sim_field": ([_P, c_int64, c_int64, _P, c_int64, c_int64, c_int64, c_double, c_double, _P, _P, _P, _P, c_size_t, _P], c_int32),
-    "scint_sim_last_route": ([POINTER(c_int32), POINTER(c_int64)], c_int32),
-    "scint_sim_pulse": ([_P, c_int64, c_int64, _P, _P, _P], c_int32),
-    "scint_acf_model_workspace_bytes": ([c_int64, c_int64, c_int64, c_int64, POINTER(c_size_t)], c_int32),
-    "scint_acf_model": ([_P, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_double, c_double, c_double, c_double, c_double,
-                         c_double, _P, _P, _P, c_size_t, _P], c_int32),
-    "scint_scattered_image_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
-    "scint_scattered_image": ([_P, c_int64, c_int64, c_int64, c_int64, c_int64, _P, _P, POINTER(c_double), c_int64, _P, _P, _P,
-                               POINTER(c_double), c_int64, c_int64, _P, _P, c_double, c_int64, _P, _P, _P, c_size_t, _P], c_int32),
-    "scint_zap_workspace_bytes": ([POINTER(c_size_t)], c_int32),
-    "scint_zap": ([_P, c_int64, c_double, _P, _P, c_size_t, _P], c_int32),
-    "scint_refill_median": ([_P, c_int64, c_int64, c_int64, c_int64, c_double, _P, _P], c_int32),
-    "scint_refill_linear": ([_P, c_int64, c_int64, c_int32, _P, _P], c_int32),
-    "scint_svd_model_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
-    "scint_svd_model": ([_P, c_int64, c_int64, c_int32, _P, c_double, c_int32, _P, _P, _P, POINTER(c_int32), _P, c_size_t, _P],
-                        c_int32),
-    "scint_nanmean_axis_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
-    "scint_nanmean_axis": ([_P, c_int64, c_int64, c_int32, _P, _P, c_size_t, _P], c_int32),
-    "scint_divide_axis": ([_P, c_int64, c_int64, c_int32, _P, _P], c_int32),
-    "scint_slow_ft_workspace_bytes": ([c_int64, c_int64, POINTER(c_size_t)], c_int32),
-    "scint_slow_ft": ([_P, c_int64, c_int64, _P, _P, _P, c_size_t, _P], c_int32),
-}
+# ---- the binding is derived from include/scint_hip.h -------------------------------------------------------------------
+_SCALARS = {"int32_t": c_int32, "int64_t": c_int64, "double": c_double, "size_t": c_size_t}
+_HOST_POINTEES = dict(_SCALARS, char=ctypes.c_char, scint_cs_geom=CsGeom, scint_thin_geom=ThinGeom)
+_DEVICE_POINTEES = ("scint_c128", "double", "float", "int32_t", "int64_t", "uint8_t", "void")
+_STRUCTS = {"scint_cs_geom": CsGeom, "scint_thin_geom": ThinGeom}
+# Entry points whose int32_t is a VALUE (a count, a mode), not a status: `call` hands it back instead of checking it.
+_RETURNS_VALUE = frozenset(("scint_version", "scint_device_count", "scint_sweep_precision", "scint_sweep_workgroups"))
+
+# kind: "scalar" | "host" | "device"; ctype: the argtype; pointee: the type name the header gives a pointer's target
+Param = collections.namedtuple("Param", "name kind ctype pointee const")
+
+
+def _strip_comments(text):
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+
+
+def _symbols(text):
+    return sorted(set(re.findall(r"\b(scint_[a-z0-9_]+)\s*\(", text)))
+
+
+def _parse_param(decl, proto):
+    m = re.fullmatch(r"(const\s+)?(\w+)\s*(\*)?\s*(SCINT_HOST)?\s*(\w+)", decl.strip())
+    if not m:
+        raise ValueError(f"scint_hip.h: cannot read parameter `{decl.strip()}` of `{proto}`")
+    const, typ, star, host, name = m.groups()
+    if not star:
+        if typ not in _SCALARS or host:
+            raise ValueError(f"scint_hip.h: unknown type `{typ}` of parameter `{name}` of `{proto}`")
+        return Param(name, "scalar", _SCALARS[typ], typ, True)
+    if host:
+        if typ not in _HOST_POINTEES:
+            raise ValueError(f"scint_hip.h: unknown host pointee `{typ}` of parameter `{name}` of `{proto}`")
+        return Param(name, "host", c_char_p if typ == "char" else POINTER(_HOST_POINTEES[typ]), typ, bool(const))
+    if typ not in _DEVICE_POINTEES:
+        raise ValueError(f"scint_hip.h: unknown device pointee `{typ}` of parameter `{name}` of `{proto}`")
+    return Param(name, "device", c_void_p, typ, bool(const))
+
+
+def parse_header(text):
+    """(SCINT_ABI_VERSION, {entry point: [Param, ...]}) of a header text.  Raises ValueError for anything it cannot read: a
+    prototype the strict pattern misses, an unknown type, a geometry struct that differs from its ctypes mirror."""
+    text = _strip_comments(text)
+    ver = re.search(r"^\s*#\s*define\s+SCINT_ABI_VERSION\s+(\d+)\s*$", text, flags=re.M)
+    if not ver:
+        raise ValueError("scint_hip.h: no `#define SCINT_ABI_VERSION <number>`")
+    protos = {}
+    for m in re.finditer(r"\bint32_t\s+(scint_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        proto = " ".join(m.group(0).split())
+        args = m.group(2).strip()
+        protos[m.group(1)] = [] if args == "void" else [_parse_param(d, proto) for d in args.split(",")]
+    unread = sorted(set(_symbols(text)) - set(protos))
+    if unread:
+        raise ValueError(f"scint_hip.h: cannot read the prototype of {', '.join(unread)} "
+                         "(expected `int32_t scint_name(type name, ...);`)")
+    for m in re.finditer(r"typedef\s+struct\s*\{([^}]*)\}\s*(\w+)\s*;", text):
+        mirror = _STRUCTS.get(m.group(2))
+        if mirror is None:
+            continue
+        want = []
+        for decl in filter(None, (d.strip() for d in m.group(1).split(";"))):      # `double tau0, dtau`
+            typ, names = decl.split(None, 1)
+            want += [(n.strip(), _SCALARS.get(typ)) for n in names.split(",")]
+        if want != list(mirror._fields_) or ctypes.sizeof(mirror) != sum(ctypes.sizeof(t) for _, t in want):
+            raise ValueError(f"scint_hip.h: {m.group(2)} has fields {[n for n, _ in want]} ({len(want)}), "
+                             f"{mirror.__name__} mirrors {[n for n, _ in mirror._fields_]} ({len(mirror._fields_)})")
+    return int(ver.group(1)), protos
+
+
+with open(HEADER_PATH) as _fh:
+    ABI_VERSION, _PARAMS = parse_header(_fh.read())       # ABI_VERSION: scint_version() of the library this binding describes
+_SIGNATURES = {name: ([p.ctype for p in params], c_int32) for name, params in _PARAMS.items()}
 
 _lib = None
-ABI_VERSION = 108          # scint_version() of the library these signatures describe (csrc/capi.hip)
 
 
 def header_symbols():
     """Names of every function declared in include/scint_hip.h."""
     with open(HEADER_PATH) as fh:
-        text = fh.read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(scint_[a-z0-9_]+)\s*\(", text)))
+        return _symbols(_strip_comments(fh.read()))
+
+
+# ---- one checked way across the boundary -------------------------------------------------------------------------------
+def _device_dtypes(torch):
+    return {"scint_c128": (torch.complex128,), "double": (torch.float64,), "float": (torch.float32, torch.complex64),
+            "int32_t": (torch.int32,), "int64_t": (torch.int64,), "uint8_t": (torch.uint8,), "void": None}
+
+
+def _converter(fn_name, p, torch):
+    """The function that checks one argument of `fn_name` against parameter `p` and turns it into what ctypes passes.  It only
+    checks: an array or tensor of the wrong type, layout or residence is a TypeError, never a silent copy."""
+    where = f"{fn_name}: parameter `{p.name}`"
+    if p.kind == "scalar":
+        return float if p.ctype is c_double else operator.index      # (a float for a size is a TypeError, not truncated)
+    if p.kind == "device":
+        dtypes = _device_dtypes(torch)[p.pointee]
+        expect = f"a contiguous torch tensor of {p.pointee}" + (", an address" if dtypes is None else "") + " or None"
+
+        def device(t):
+            if t is None:
+                return None
+            if isinstance(t, torch.Tensor):
+                if dtypes is not None and t.dtype not in dtypes:
+                    raise TypeError(f"{where} is `{p.pointee}*` device memory: expected {expect}, got a tensor of {t.dtype}")
+                if not t.is_contiguous():
+                    raise TypeError(f"{where}: expected {expect}, got a non-contiguous tensor")
+                return t.data_ptr()
+            if dtypes is None and type(t) is int:
+                return t
+            raise TypeError(f"{where} is `{p.pointee}*` device memory: expected {expect}, got {type(t).__name__}")
+        return device
+    ctype = _HOST_POINTEES[p.pointee]
+    dtype = np.dtype(ctype) if p.pointee in _SCALARS else None
+    expect = (f"a C-contiguous{'' if p.const else ' writeable'} NumPy array of {dtype}, " if dtype is not None else "") + \
+        f"a ctypes {ctype.__name__} (or an array of them) or None"
+
+    def host(a):
+        if a is None:
+            return None
+        if isinstance(a, np.ndarray):
+            if dtype is None or a.dtype != dtype:
+                raise TypeError(f"{where} is `{p.pointee}*` host memory: expected {expect}, got an array of {a.dtype}")
+            if not a.flags.c_contiguous:
+                raise TypeError(f"{where}: expected {expect}, got a non-contiguous array")
+            if not (p.const or a.flags.writeable):
+                raise TypeError(f"{where} is written by the call: expected {expect}, got a read-only array")
+            return a.ctypes.data_as(p.ctype)
+        if isinstance(a, ctype):
+            return ctypes.byref(a)
+        if isinstance(a, ctypes.Array) and a._type_ is ctype:
+            return a
+        raise TypeError(f"{where} is `{p.pointee}*` host memory: expected {expect}, got {type(a).__name__}")
+    return host
+
+
+def bind(lib):
+    """Give every entry point of a loaded library (the product's, or the emulated one of the tests) the argument types the
+    header declares and the converters `call` uses.  Returns `lib`.  AttributeError, as ctypes' own, if it lacks a symbol."""
+    import torch
+    missing = [name for name in _PARAMS if not hasattr(lib, name)]
+    if missing:
+        raise AttributeError(f"{getattr(lib, '_name', lib)} lacks {', '.join(missing)}, which include/scint_hip.h declares")
+    lib._calls = {}
+    for name, params in _PARAMS.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = _SIGNATURES[name]
+        lib._calls[name] = (fn, [_converter(name, p, torch) for p in params])
+    return lib
+
+
+def call(name, *args):
+    """Call entry point `name`: every argument is checked against the header's parameter (scalar, host pointer, device
+    pointer -- TypeError before the library is entered) and the status is checked (ScintHipError).  Returns None, or the
+    value of the few entry points that return one (scint_version, scint_sweep_precision, ...)."""
+    lib = load()
+    try:
+        fn, convs = lib._calls[name]
+    except AttributeError:             # a library handle that was put in place without `bind` (tests may do that)
+        fn, convs = bind(lib)._calls[name]
+    if len(args) != len(convs):
+        raise TypeError(f"{name} takes {len(convs)} arguments ({len(args)} given)")
+    rc = fn(*[conv(a) for conv, a in zip(convs, args)])
+    if name in _RETURNS_VALUE:
+        return rc
+    check(rc, name)
 
 
 def load():
@@ -182,18 +226,13 @@ def load():
     # loaded so that both bind the same runtime (loading ours first leaves the process with two
     # runtimes and ours then sees no device).
     import torch  # noqa: F401
-    lib = ctypes.CDLL(LIB_PATH)
     # An entry point may be ADDED without a new ABI version (the version guards the argument lists of the existing ones): a stale
     # build that lacks one must say so here, not fail with an AttributeError in the middle of a call.
-    missing = [name for name in _SIGNATURES if not hasattr(lib, name)]
-    if missing:
-        raise ScintHipError(f"{LIB_PATH} lacks {', '.join(missing)}: it was built from older sources; "
-                            "rebuild it with `python -m scintools_amd.build`")
-    for name, (argtypes, restype) in _SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = restype
-    # The signatures above describe ONE version of the C ABI (an argument added in the middle of a list shifts every
+    try:
+        lib = bind(ctypes.CDLL(LIB_PATH))
+    except AttributeError as err:
+        raise ScintHipError(f"{err}: it was built from older sources; rebuild it with `python -m scintools_amd.build`") from None
+    # The header describes ONE version of the C ABI (an argument added in the middle of a list shifts every
     # pointer after it): a stale build must fail here, not corrupt memory in its first call.
     got = lib.scint_version()
     if got != ABI_VERSION:
@@ -211,7 +250,9 @@ def last_error():
 
 def check(rc, what=""):
     if rc != SCINT_OK:
-        raise ScintHipError(f"{what or 'libscint_hip call'} failed (status {rc}): {last_error()}")
+        err = ScintHipError(f"{what or 'libscint_hip call'} failed (status {rc}): {last_error()}")
+        err.status = rc
+        raise err
 
 
 def require_gpu():

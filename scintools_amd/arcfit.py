@@ -20,7 +20,7 @@ import torch
 from scipy.signal import savgol_filter
 
 from . import _lib
-from .device import empty, ptr, require_gpu, stream_ptr, to_device, workspace
+from .device import empty, require_gpu, stream_ptr, to_device, workspace, workspace_for
 
 
 def is_valid(array):
@@ -102,7 +102,6 @@ def _spline_warm(sub, inv, sup, n):
 def spline_resample_device(dyn_t, freqs, feq):
     """Cubic-spline (scipy ``interp1d(kind='cubic')``) resample of every time column of the
     device array dyn_t[nf, nt] from `freqs` to `feq`, rows flipped (dynspec.py:3948-3957)."""
-    lib = _lib.load()
     require_gpu()
     freqs = np.asarray(freqs, dtype=float)
     nf, nt = (int(v) for v in dyn_t.shape)
@@ -137,7 +136,7 @@ def spline_resample_device(dyn_t, freqs, feq):
         # the unblocked sweep) does; warm-started blocks would confine it to one block.  One
         # device reduction tells: the mean is non-finite iff some pixel is.
         m = ctypes.c_double()
-        _lib.check(lib.scint_mean(ptr(dyn_t), nf * nt, ctypes.byref(m), stream_ptr()), "scint_mean")
+        _lib.call("scint_mean", dyn_t, nf * nt, m, stream_ptr())
         if not np.isfinite(m.value):
             block_rows, warm = 0, 0
     ws = workspace.get(2 * 8 * nf * nt)
@@ -145,10 +144,8 @@ def spline_resample_device(dyn_t, freqs, feq):
     dev = lambda v: to_device(np.ascontiguousarray(v, dtype=float), torch.float64)
     h_t, sub_t, inv_t, sup_t, coef_t = dev(h), dev(sub), dev(inv), dev(sup), dev(coef)
     idx_t = to_device(idx.astype(np.int32), torch.int32)
-    rc = lib.scint_spline_resample(ptr(dyn_t), nf, nt, reverse, ptr(h_t), ptr(sub_t), ptr(inv_t), ptr(sup_t),
-                                   end.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), block_rows, warm,
-                                   ptr(idx_t), ptr(coef_t), len(feq), ptr(out), ptr(ws), ws.numel(), stream_ptr())
-    _lib.check(rc, "scint_spline_resample")
+    _lib.call("scint_spline_resample", dyn_t, nf, nt, reverse, h_t, sub_t, inv_t, sup_t, end, block_rows, warm, idx_t, coef_t,
+              len(feq), out, ws, ws.numel(), stream_ptr())
     return out
 
 
@@ -217,7 +214,6 @@ def norm_sspec(self, eta=None, delmax=None, plot=False, startbin=1, maxnormfac=5
         raise NotImplementedError("interp_nan (scipy.interpolate.griddata) is outside the accelerated path")
     if fit_spectrum:
         raise NotImplementedError("fit_spectrum needs lmfit and is outside the accelerated path")
-    lib = _lib.load()
     require_gpu()
     if not hasattr(self, "tdel"):
         self.calc_sspec(lamsteps=lamsteps)
@@ -256,8 +252,7 @@ def norm_sspec(self, eta=None, delmax=None, plot=False, startbin=1, maxnormfac=5
         colsel = (np.abs(fdop) > 0.9 * np.max(fdop)).astype(np.uint8)
         colsel_t = to_device(colsel, torch.uint8)
         resp_t = empty((nr,), torch.float64)
-        _lib.check(lib.scint_row_nanmean(ptr(sspec_t), nc, nc, row0, nr, ptr(colsel_t), cut_lo, cut_hi,
-                                         ptr(resp_t), stream_ptr()), "scint_row_nanmean")
+        _lib.call("scint_row_nanmean", sspec_t, nc, nc, row0, nr, colsel_t, cut_lo, cut_hi, resp_t, stream_ptr())
         resp = resp_t.cpu().numpy()
         resp -= np.median(resp)
         offset_t = to_device(resp, torch.float64)
@@ -289,10 +284,8 @@ def norm_sspec(self, eta=None, delmax=None, plot=False, startbin=1, maxnormfac=5
     norm_t = empty((nr, nx), torch.float64)
     mask_t = empty((nr, nx), torch.uint8)
     pow_t = empty((nr,), torch.float64)
-    rc = lib.scint_norm_sspec(ptr(sspec_t), nc, nc, ptr(fdop_t), ptr(yaxis_t), row0, nr, eta,
-                              float(maxnormfac), cut_lo, cut_hi, ptr(offset_t), ptr(x_t), ptr(xlin_t), nx,
-                              ptr(norm_t), ptr(mask_t), ptr(pow_t), stream_ptr())
-    _lib.check(rc, "scint_norm_sspec")
+    _lib.call("scint_norm_sspec", sspec_t, nc, nc, fdop_t, yaxis_t, row0, nr, eta, maxnormfac, cut_lo, cut_hi, offset_t, x_t, xlin_t,
+              nx, norm_t, mask_t, pow_t, stream_ptr())
     self.powerspectrum = np.ma.masked_invalid(pow_t.cpu().numpy())
     xdata = np.sqrt(tdel)
     ydata = np.sqrt(tdel) * self.powerspectrum
@@ -316,14 +309,10 @@ def norm_sspec(self, eta=None, delmax=None, plot=False, startbin=1, maxnormfac=5
         rowsel[np.argwhere(np.ma.filled(arc_spectrum > wn, False)).ravel()] = 1
         rowsel_t = to_device(rowsel, torch.uint8)
     w_t = to_device(np.ascontiguousarray(wts), torch.float64)
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_masked_colavg_workspace_bytes(nr, nx, ctypes.byref(need)), "masked_colavg_workspace_bytes")
-    ws = workspace.get(need.value)
+    ws = workspace_for("scint_masked_colavg", nr, nx)
     avg_t = empty((nx,), torch.float64)
     none_t = empty((nx,), torch.uint8)
-    rc = lib.scint_masked_colavg(ptr(norm_t), ptr(mask_t), nr, nx, ptr(w_t), ptr(rowsel_t), ptr(avg_t),
-                                 ptr(none_t), ptr(ws), ws.numel(), stream_ptr())
-    _lib.check(rc, "scint_masked_colavg")
+    _lib.call("scint_masked_colavg", norm_t, mask_t, nr, nx, w_t, rowsel_t, avg_t, none_t, ws, ws.numel(), stream_ptr())
     # a column with no unmasked entry is masked, with numpy.ma's 0.0 left under the mask
     self.normsspecavg = np.ma.array(avg_t.cpu().numpy(), mask=none_t.cpu().numpy().astype(bool))
     self._normsspec_dev = (norm_t, mask_t)
@@ -385,7 +374,6 @@ def fit_arc(self, asymm=False, plot=False, delmax=None, numsteps=1e4, startbin=3
         raise NotImplementedError("plotting is outside the accelerated hot path")
     if velocity:
         raise NotImplementedError("velocity scaling needs Dynspec.scale_dyn('velocity') (outside the hot path)")
-    lib = _lib.load()
     require_gpu()
     if not hasattr(self, "tdel"):
         self.calc_sspec()
@@ -400,9 +388,7 @@ def fit_arc(self, asymm=False, plot=False, delmax=None, numsteps=1e4, startbin=3
     c_lo = int(nc / 2 - np.floor(cutmid / 2))
     std_t = empty((1,), torch.float64)
     ws = workspace.get(8 * 1032)
-    rc = lib.scint_block_std(ptr(sspec_t), nc, nc, int(nr / 2), nr, c_lo, c_hi, ptr(std_t), ptr(ws),
-                             ws.numel(), stream_ptr())
-    _lib.check(rc, "scint_block_std")
+    _lib.call("scint_block_std", sspec_t, nc, nc, int(nr / 2), nr, c_lo, c_hi, std_t, ws, ws.numel(), stream_ptr())
     noise = float(std_t.cpu().numpy()[0])
     yaxis = yaxis[0:ind]
     noise = np.sqrt(np.sum(np.power(noise, 2))) / np.sqrt(len(yaxis) * 2)
@@ -541,7 +527,6 @@ def scattered_image_device(sspec_t, rows, cols, tdel, fdop, eta, sampling):
     [cols[0], cols[1]), with the cropped knots tdel / fdop (any strictly increasing spacing): the interpolating bicubic
     not-a-knot spline of 10**(sspec/10) evaluated through eta, times fdop_y, mirrored (``scint_scattered_image``).  Returns
     (image, fdop_x).  The Thomas factors, the intervals and the abscissae are host NumPy, handed over as data."""
-    lib = _lib.load()
     require_gpu()
     tdel = np.ascontiguousarray(tdel, dtype=float)
     fdop = np.ascontiguousarray(fdop, dtype=float)
@@ -579,18 +564,14 @@ def scattered_image_device(sspec_t, rows, cols, tdel, fdop, eta, sampling):
     dev = lambda v: to_device(np.ascontiguousarray(v, dtype=float), torch.float64)
     tdel_t, row_sys_t, coef_t, col_sys_t, fx_t, fy_t = dev(tdel), dev(row_sys), dev(coef), dev(col_sys), dev(fdop_x), dev(fdop_y)
     idx_t = to_device(idx.astype(np.int32), torch.int32)
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_scattered_image_workspace_bytes(nrow, sampling, ctypes.byref(need)), "scattered_image_workspace_bytes")
-    ws = workspace.get(need.value)
+    ws = workspace_for("scint_scattered_image", nrow, sampling)
     image_t = empty((nx, nx), torch.float64)
     flag_t = empty((1,), torch.int32)
-    as_c = lambda v: v.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
     end, endc = np.ascontiguousarray(end, dtype=float), np.ascontiguousarray(endc, dtype=float)
-    rc = lib.scint_scattered_image(ptr(sspec_t), int(sspec_t.stride(0)), int(rows[0]), int(rows[1]), int(cols[0]), int(cols[1]),
-                                   ptr(tdel_t), ptr(row_sys_t), as_c(end), int(row_warm), ptr(idx_t), ptr(coef_t), ptr(col_sys_t),
-                                   as_c(endc), int(block_rows), int(col_warm), ptr(fx_t), ptr(fy_t), float(eta), int(sampling),
-                                   ptr(image_t), ptr(flag_t), ptr(ws), ws.numel(), stream_ptr())
-    _lib.check(rc, "scint_scattered_image")
+    _lib.call("scint_scattered_image", sspec_t, sspec_t.stride(0), int(rows[0]), int(rows[1]), int(cols[0]), int(cols[1]), tdel_t,
+              row_sys_t, end, int(row_warm), idx_t, coef_t, col_sys_t, endc, int(block_rows), int(col_warm), fx_t, fy_t, eta,
+              int(sampling), image_t, flag_t,
+              ws, ws.numel(), stream_ptr())
     image = image_t.cpu().numpy()
     if int(flag_t.cpu().numpy()[0]):
         # a NaN or inf in 10**(sspec/10): FITPACK's global solve spreads it over every coefficient and scipy returns NaN

@@ -24,7 +24,6 @@ import numpy as np
 import torch
 
 from . import _lib, device
-from .device import ptr
 
 SVD_TOL = 1e-12            # = ththmod.DEFAULT_TOL (tests/test_clean_cpu.py checks that they agree)
 SVD_MAX_ITER = 4000
@@ -43,9 +42,8 @@ def is_valid(array):
 
 
 def _lib_ready():
-    lib = _lib.load()
+    _lib.load()
     device.require_gpu()
-    return lib
 
 
 # ----------------------------------------------------------------------------
@@ -53,14 +51,11 @@ def _lib_ready():
 # ----------------------------------------------------------------------------
 def zap_device(dyn, sigma=7):
     """(zapped copy of ``dyn``, median, mdev) of ``Dynspec.zap`` from the device (``scint_zap``)."""
-    lib = _lib_ready()
+    _lib_ready()
     t = device.to_device(np.array(dyn, dtype=np.float64), torch.float64)
     stats = device.empty((2,), torch.float64)
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_zap_workspace_bytes(ctypes.byref(need)), "zap_workspace_bytes")
-    ws = device.workspace.get(need.value)
-    _lib.check(lib.scint_zap(ptr(t), int(t.numel()), float(sigma), ptr(stats), ptr(ws), ws.numel(), device.stream_ptr()),
-               "scint_zap")
+    ws = device.workspace_for("scint_zap")
+    _lib.call("scint_zap", t, t.numel(), sigma, stats, ws, ws.numel(), device.stream_ptr())
     med, mdev = (float(v) for v in stats.cpu().numpy())
     return t.cpu().numpy(), med, mdev
 
@@ -84,21 +79,21 @@ def _kernel_size(kernel_size):
 
 def median_fill_device(dyn, kf, kt, fill):
     """``dyn`` with every NaN replaced by the median of its kf x kt window of ``dyn with NaN -> fill`` (zero padded)."""
-    lib = _lib_ready()
+    _lib_ready()
     t = device.to_device(dyn, torch.float64)
     nf, nt = (int(v) for v in t.shape)
     out = device.empty((nf, nt), torch.float64)
-    _lib.check(lib.scint_refill_median(ptr(t), nf, nt, kf, kt, float(fill), ptr(out), device.stream_ptr()), "scint_refill_median")
+    _lib.call("scint_refill_median", t, nf, nt, kf, kt, fill, out, device.stream_ptr())
     return out.cpu().numpy()
 
 
 def linear_fill_device(dyn, axis, line_valid):
     """A copy of ``dyn`` with the lines (axis 0: channels, axis 1: sub-integrations) flagged invalid interpolated across."""
-    lib = _lib_ready()
+    _lib_ready()
     t = device.to_device(np.array(dyn, dtype=np.float64), torch.float64)
     nf, nt = (int(v) for v in t.shape)
     v = device.to_device(np.asarray(line_valid, dtype=np.uint8), torch.uint8)
-    _lib.check(lib.scint_refill_linear(ptr(t), nf, nt, int(axis), ptr(v), device.stream_ptr()), "scint_refill_linear")
+    _lib.call("scint_refill_linear", t, nf, nt, int(axis), v, device.stream_ptr())
     return t.cpu().numpy()
 
 
@@ -115,27 +110,27 @@ def _start_basis(nt, p):
 
 def svd_device(arr, p, want_corrected=True, info=None):
     """(model, arr / |model|) of the real 2-D ``arr`` from its top ``p`` singular triplets (``scint_svd_model``)."""
-    lib = _lib_ready()
+    _lib_ready()
     t = device.to_device(arr, torch.float64)
     nf, nt = (int(v) for v in t.shape)
     v0 = device.to_device(_start_basis(nt, p), torch.float64)
     model = device.empty((nf, nt), torch.float64)
     corrected = device.empty((nf, nt), torch.float64) if want_corrected else None
     status = device.empty((12,), torch.float64)
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_svd_model_workspace_bytes(nf, nt, ctypes.byref(need)), "svd_model_workspace_bytes")
-    ws = device.workspace.get(need.value)
+    ws = device.workspace_for("scint_svd_model", nf, nt)
     iters = ctypes.c_int32()
-    rc = lib.scint_svd_model(ptr(t), nf, nt, int(p), ptr(v0), SVD_TOL, SVD_MAX_ITER, ptr(model), ptr(corrected), ptr(status),
-                             ctypes.byref(iters), ptr(ws), ws.numel(), device.stream_ptr())
-    if rc == _lib.SCINT_E_NONFINITE:
-        raise ValueError("svd_model: the array holds a NaN or an infinite element (numpy.linalg.svd does not converge either)")
-    if rc == _lib.SCINT_E_NOCONV:
-        st = status.cpu().numpy()
-        raise _lib.ScintHipError(f"svd_model: the block iteration stopped after {iters.value} steps at a residual of {st[0]:.3g} "
-                                 f"(wanted {SVD_TOL:g} * {st[1]:.3g}): singular values {p} and {p + 1} are too close, or mode {p} "
-                                 "is below 3 % of the first")
-    _lib.check(rc, "scint_svd_model")
+    try:
+        _lib.call("scint_svd_model", t, nf, nt, int(p), v0, SVD_TOL, SVD_MAX_ITER, model, corrected, status, iters, ws, ws.numel(),
+                  device.stream_ptr())
+    except _lib.ScintHipError as err:
+        if err.status == _lib.SCINT_E_NONFINITE:
+            raise ValueError("svd_model: the array holds a NaN or an infinite element (numpy.linalg.svd does not converge either)") from None
+        if err.status == _lib.SCINT_E_NOCONV:
+            st = status.cpu().numpy()
+            raise _lib.ScintHipError(f"svd_model: the block iteration stopped after {iters.value} steps at a residual of {st[0]:.3g} "
+                                     f"(wanted {SVD_TOL:g} * {st[1]:.3g}): singular values {p} and {p + 1} are too close, or mode {p} "
+                                     "is below 3 % of the first") from None
+        raise
     if info is not None:
         st = status.cpu().numpy()
         info.update(iters=iters.value, residual=st[0], lam_min=st[1], lam_max=st[2], active=int(st[3]), lam=st[4:4 + p].copy())
@@ -169,23 +164,20 @@ def svd_model(arr, nmodes=1, info=None):
 
 def nanmean_device(t, axis):
     """np.nanmean of the device array ``t`` along ``axis`` as a host vector."""
-    lib = _lib.load()
     nf, nt = (int(v) for v in t.shape)
     out = device.empty((nf if axis == 1 else nt,), torch.float64)
     need = ctypes.c_size_t()
-    _lib.check(lib.scint_nanmean_axis_workspace_bytes(nf, nt, ctypes.byref(need)), "nanmean_axis_workspace_bytes")
-    ws = device.workspace.get(max(need.value, 256))
-    _lib.check(lib.scint_nanmean_axis(ptr(t), nf, nt, int(axis), ptr(out), ptr(ws), ws.numel(), device.stream_ptr()),
-               "scint_nanmean_axis")
+    _lib.call("scint_nanmean_axis_workspace_bytes", nf, nt, need)
+    ws = device.workspace.get(max(need.value, 256))        # (axis 1 needs none: never a null pointer)
+    _lib.call("scint_nanmean_axis", t, nf, nt, int(axis), out, ws, ws.numel(), device.stream_ptr())
     return out.cpu().numpy()
 
 
 def divide_device(t, axis, vec):
     """t[i][j] /= vec[i] (axis 0) or vec[j] (axis 1), in place on the device."""
-    lib = _lib.load()
     nf, nt = (int(v) for v in t.shape)
     v = device.to_device(np.ascontiguousarray(vec, dtype=float), torch.float64)
-    _lib.check(lib.scint_divide_axis(ptr(t), nf, nt, int(axis), ptr(v), device.stream_ptr()), "scint_divide_axis")
+    _lib.call("scint_divide_axis", t, nf, nt, int(axis), v, device.stream_ptr())
 
 
 # ----------------------------------------------------------------------------

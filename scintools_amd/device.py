@@ -3,6 +3,7 @@
 No torch op runs inside the hot loop -- tensors are allocated here and their
 ``data_ptr()`` is handed to the HIP kernels through the C ABI.
 """
+import ctypes
 import threading
 
 import numpy as np
@@ -24,6 +25,8 @@ def stream_ptr():
 
 
 def ptr(t):
+    """Bare address of a tensor, for the direct ``lib.scint_*`` calls of bench.py, the tools and the tests (the package
+    itself goes through ``_lib.call``, which checks dtype and layout)."""
     return None if t is None else t.data_ptr()
 
 
@@ -80,6 +83,13 @@ class _PerThreadWorkspace:
 
 
 workspace = _PerThreadWorkspace()
+
+
+def workspace_for(name, *size_args):
+    """The calling thread's scratch buffer, grown to what ``<name>_workspace_bytes(*size_args)`` asks for."""
+    need = ctypes.c_size_t()
+    _lib.call(name + "_workspace_bytes", *size_args, need)
+    return workspace.get(need.value)
 
 
 class DeviceBacked:

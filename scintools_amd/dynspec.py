@@ -23,7 +23,6 @@ reference ``Dynspec``, or plain arrays) with
 
 Velocity / trapezoid rescaling, ``cut_dyn`` and plotting are out of scope.
 """
-import ctypes
 import functools
 import os
 import warnings
@@ -34,7 +33,8 @@ import torch
 
 from . import _lib, arcfit, clean, psrflux, units
 from . import ththmod as thth
-from .device import DeviceBacked, empty, ptr, require_gpu, stream_ptr, to_device, workspace
+from .device import DeviceBacked, empty, require_gpu, stream_ptr, to_device, workspace_for
+from .device import workspace  # noqa: F401  (kept as a module attribute: the host-interpreter tests swap it per module)
 
 _WINDOWS = {"hanning": np.hanning, "hamming": np.hamming,
             "blackman": np.blackman, "bartlett": np.bartlett}
@@ -84,7 +84,6 @@ def _postdark_tables(nrfft, ncfft, device):
 def sspec_device(dyn_t, prewhite=False, halve=True, window="hanning", window_frac=0.1):
     """Secondary spectrum of a device dynamic spectrum [nf, nt] float64 -> device
     tensor in dB, shape [(nrfft/2 if halve else nrfft), ncfft] (dynspec.py:3665-3721)."""
-    lib = _lib.load()
     require_gpu()
     nf, nt = (int(v) for v in dyn_t.shape)
     nrfft = int(2 ** (np.ceil(np.log2(nf)) + 1))      # dynspec.py:3677
@@ -93,14 +92,10 @@ def sspec_device(dyn_t, prewhite=False, halve=True, window="hanning", window_fra
         raise RuntimeError("Cannot apply prewhite to full frame")   # dynspec.py:3717
     wt, wf = _window_tables(nt, nf, window, window_frac, torch.cuda.current_device())
     pd_fd, pd_td = _postdark_tables(nrfft, ncfft, torch.cuda.current_device()) if prewhite else (None, None)
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_sspec_workspace_bytes(nf, nt, ctypes.byref(need)), "sspec_workspace_bytes")
-    ws = workspace.get(need.value)
+    ws = workspace_for("scint_sspec", nf, nt)
     out = empty((nrfft // 2 if halve else nrfft, ncfft), torch.float64)
-    rc = lib.scint_sspec(ptr(dyn_t), nf, nt, ptr(wt), ptr(wf), 1 if prewhite else 0,
-                         1 if halve else 0, ptr(pd_fd), ptr(pd_td), ptr(out), ptr(ws), ws.numel(),
-                         stream_ptr())
-    _lib.check(rc, "scint_sspec")
+    _lib.call("scint_sspec", dyn_t, nf, nt, wt, wf, 1 if prewhite else 0, 1 if halve else 0, pd_fd, pd_td, out, ws, ws.numel(),
+              stream_ptr())
     return out
 
 
@@ -291,21 +286,16 @@ class Dynspec:
         only excludes them from the mean); method='sspec' is outside the hot path."""
         if method != 'direct':
             raise NotImplementedError("calc_acf(method='sspec') is outside the accelerated hot path")
-        lib = _lib.load()
         require_gpu()
         dyn = self.dyn if input_dyn is None else np.asarray(input_dyn)
         if not np.all(np.isfinite(dyn)):
             raise ValueError("calc_acf on the GPU needs a finite dynamic spectrum (run refill first)")
         dyn_t = to_device(dyn, torch.float64)
         nf, nt = (int(v) for v in dyn_t.shape)
-        need = ctypes.c_size_t()
-        _lib.check(lib.scint_acf_workspace_bytes(nf, nt, ctypes.byref(need)), "acf_workspace_bytes")
-        ws = workspace.get(need.value)
+        ws = workspace_for("scint_acf", nf, nt)
         out = empty((2 * nf, 2 * nt), torch.float64)
         # with input_dyn the reference does NOT subtract the mean (dynspec.py:3786-3789)
-        rc = lib.scint_acf(ptr(dyn_t), nf, nt, 1 if input_dyn is None else 0, 1 if normalise else 0, ptr(out),
-                           ptr(ws), ws.numel(), stream_ptr())
-        _lib.check(rc, "scint_acf")
+        _lib.call("scint_acf", dyn_t, nf, nt, 1 if input_dyn is None else 0, 1 if normalise else 0, out, ws, ws.numel(), stream_ptr())
         arr = out.cpu().numpy()
         if input_dyn is None:
             self.acf = arr

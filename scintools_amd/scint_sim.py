@@ -55,7 +55,7 @@ def last_route():
     """(column, groups) of the last field computation of the process: whether it took the column shortcut (False with
     SCINT_SIM_COLUMN=0) and the number of frequency groups it ran."""
     col, groups = ctypes.c_int32(), ctypes.c_int64()
-    _lib.check(_lib.load().scint_sim_last_route(ctypes.byref(col), ctypes.byref(groups)), "scint_sim_last_route")
+    _lib.call("scint_sim_last_route", col, groups)
     return bool(col.value), int(groups.value)
 
 
@@ -166,7 +166,6 @@ class Simulation:
     def get_screen(self):
         """w and xyp = real(fft2(w (z1 + 1j z2))) (scint_sim.py:169-207); the normals are the reference's for the seed."""
         dev = device.require_gpu()
-        lib = _lib.load()
         nx, ny = self.nx, self.ny
         rs = np.random.RandomState(self.seed)
         z1 = torch.from_numpy(rs.randn(nx, ny)).to(dev)
@@ -181,14 +180,11 @@ class Simulation:
         a = (cs**2) / r + r * sn**2
         b = r * cs**2 + sn**2 / r
         c = 2 * cs * sn * (1 / r - r)
-        need = ctypes.c_size_t()
-        _lib.check(lib.scint_sim_screen_workspace_bytes(nx, ny, ctypes.byref(need)), "scint_sim_screen_workspace_bytes")
-        ws = device.workspace.get(need.value)
+        ws = device.workspace_for("scint_sim_screen", nx, ny)
         w = torch.empty((nx, ny), dtype=torch.float64, device=dev)
         xyp = torch.empty((nx, ny), dtype=torch.float64, device=dev)
-        _lib.check(lib.scint_sim_screen(device.ptr(z1), device.ptr(z2), nx, ny, float(dqx), float(dqy), float(a), float(b), float(c),
-                                        float(con), float(alf), float(self.inner**2), device.ptr(w), device.ptr(xyp), device.ptr(ws),
-                                        ws.numel(), device.stream_ptr()), "scint_sim_screen")
+        _lib.call("scint_sim_screen", z1, z2, nx, ny, dqx, dqy, a, b, c, con, alf, self.inner**2, w, xyp, ws, ws.numel(),
+                  device.stream_ptr())
         self._xyp_t = xyp
         self.w = w.cpu().numpy()
         self.xyp = xyp.cpu().numpy()
@@ -207,20 +203,18 @@ class Simulation:
     def get_intensity(self, verbose=False, group_bytes=None):
         """spe [nx, nf] complex64, spi = |spe|^2 float32 and xyi [nx, ny] of the last frequency (scint_sim.py:209-244)."""
         dev = device.require_gpu()
-        lib = _lib.load()
         nx, ny, nf = self.nx, self.ny, self.nf
         if group_bytes is None:
             group_bytes = SIM_GROUP_BYTES
             if dev.type == "cuda":
                 group_bytes = min(group_bytes, torch.cuda.mem_get_info(dev)[0] // 2)
-        one, two = ctypes.c_size_t(), ctypes.c_size_t()
-        _lib.check(lib.scint_sim_field_workspace_bytes(nx, ny, 1, ctypes.byref(one)), "scint_sim_field_workspace_bytes")
-        _lib.check(lib.scint_sim_field_workspace_bytes(nx, ny, 2, ctypes.byref(two)), "scint_sim_field_workspace_bytes")
+        one, two, need = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+        _lib.call("scint_sim_field_workspace_bytes", nx, ny, 1, one)
+        _lib.call("scint_sim_field_workspace_bytes", nx, ny, 2, two)
         per = max(1, two.value - one.value)
         group = int(min(nf, max(1, 1 + (int(group_bytes) - one.value) // per)))
-        need = ctypes.c_size_t()
-        _lib.check(lib.scint_sim_field_workspace_bytes(nx, ny, group, ctypes.byref(need)), "scint_sim_field_workspace_bytes")
-        ws = device.workspace.get(need.value)
+        _lib.call("scint_sim_field_workspace_bytes", nx, ny, group, need)
+        ws = device.workspace.get(need.value)         # (the library sizes its groups by the BYTES it is told: need, not the buffer's)
         xyp = getattr(self, "_xyp_t", None)
         if xyp is None:
             xyp = device.to_device(self.xyp, torch.float64)
@@ -228,9 +222,8 @@ class Simulation:
         spe = torch.empty((nx, nf), dtype=torch.complex64, device=dev)
         spi = torch.empty((nx, nf), dtype=torch.float32, device=dev)
         xyi = torch.empty((nx, ny), dtype=torch.float64, device=dev)
-        _lib.check(lib.scint_sim_field(device.ptr(xyp), nx, ny, device.ptr(scale), nf, 0, nf, float(self.ffconx), float(self.ffcony),
-                                       device.ptr(spe), device.ptr(spi), device.ptr(xyi), device.ptr(ws), need.value,
-                                       device.stream_ptr()), "scint_sim_field")
+        _lib.call("scint_sim_field", xyp, nx, ny, scale, nf, 0, nf, self.ffconx, self.ffcony, spe, spi, xyi, ws, need.value,
+                  device.stream_ptr())
         self._xyp_t = None
         self.xyi = xyi.cpu().numpy()
         self.spe = spe.cpu().numpy()
@@ -251,12 +244,10 @@ class Simulation:
         if not (_pow2(2 * nf) and 16 <= 2 * nf <= 8192):
             raise NotImplementedError(f"pulsewin: 2 * nf = {2 * nf} is not a power of two in [16, 8192] (the row transform's lengths)")
         dev = device.require_gpu()
-        lib = _lib.load()
         spe = torch.from_numpy(np.array(self.spe, dtype=np.complex64, order="C")).to(dev)
         win = device.to_device(np.blackman(nf), torch.float64)
         out = torch.empty((self.nx, 2 * nf), dtype=torch.float64, device=dev)
-        _lib.check(lib.scint_sim_pulse(device.ptr(spe), self.nx, nf, device.ptr(win), device.ptr(out), device.stream_ptr()),
-                   "scint_sim_pulse")
+        _lib.call("scint_sim_pulse", spe, self.nx, nf, win, out, device.stream_ptr())
         self.__dict__["pulsewin"] = np.transpose(out.cpu().numpy())
         self.__dict__["dm"] = self.xyp[:, int(self.ny / 2)] * self.dlam / np.pi
 
@@ -389,17 +380,15 @@ class ACF:
     def _device_field(snp, snp2, snx, sny, dnun, sigxn, sigyn, sqrtar, alph2, step, step2):
         """(field [nsn, ndnun] complex128 with column 0 left at zero, acf_efield [m, m]) from scint_acf_model."""
         dev = device.require_gpu()
-        lib = _lib.load()
         m, m2, nsn, ndnun = len(snp), len(snp2), len(snx), len(dnun)
         need = ctypes.c_size_t()
-        _lib.check(lib.scint_acf_model_workspace_bytes(m, m2, nsn, ndnun, ctypes.byref(need)), "scint_acf_model_workspace_bytes")
+        _lib.call("scint_acf_model_workspace_bytes", m, m2, nsn, ndnun, need)
         ws = device.workspace.get(need.value)
         d_snp, d_snp2, d_snx, d_sny, d_dnun = (device.to_device(a, torch.float64) for a in (snp, snp2, snx, sny, dnun))
         gammes = torch.empty((m, m), dtype=torch.float64, device=dev)
         gamma = torch.zeros((nsn, ndnun), dtype=torch.complex128, device=dev)
-        _lib.check(lib.scint_acf_model(device.ptr(d_snp), m, device.ptr(d_snp2), m2, device.ptr(d_snx), device.ptr(d_sny), nsn,
-                                       device.ptr(d_dnun), ndnun, sigxn, sigyn, sqrtar, alph2, step, step2, device.ptr(gammes),
-                                       device.ptr(gamma), device.ptr(ws), need.value, device.stream_ptr()), "scint_acf_model")
+        _lib.call("scint_acf_model", d_snp, m, d_snp2, m2, d_snx, d_sny, nsn, d_dnun, ndnun, sigxn, sigyn, sqrtar, alph2, step, step2,
+                  gammes, gamma, ws, need.value, device.stream_ptr())
         return gamma.cpu().numpy(), gammes.cpu().numpy()
 
     def calc_sspec(self, window='hanning', window_frac=1):

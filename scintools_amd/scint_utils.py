@@ -6,8 +6,6 @@ observing frequency across a wide band, and applies a plain FFT along frequency.
 complex array (16 nt^2 nf bytes); here the exponentials are generated inside the kernel (csrc/slowft.hpp)
 and the memory is 40 nt nf bytes.  There is no CPU fallback.
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -33,7 +31,6 @@ def slow_FT(dynspec, freqs, *, fref=None, out_device=False):
     ft = np.fft.fftfreq(ntime, 1): a complex128 ndarray [time, frequency], or the device tensor with out_device=True (its
     transpose is a conjugate spectrum [tau, fd] for ththmod.to_device / eval_sweep)."""
     dev = device.require_gpu()
-    lib = _lib.load()
     freqs = np.asarray(_bare(freqs))
     if freqs.ndim != 1:
         raise ValueError("slow_FT: freqs must be one-dimensional")
@@ -46,11 +43,8 @@ def slow_FT(dynspec, freqs, *, fref=None, out_device=False):
     nt, nf = (int(v) for v in dyn_t.shape)
     if fscale.shape[0] != nf:
         raise ValueError(f"slow_FT: {fscale.shape[0]} frequencies for {nf} channels")
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_slow_ft_workspace_bytes(nt, nf, ctypes.byref(need)), "scint_slow_ft_workspace_bytes")
-    ws = device.workspace.get(need.value)
+    ws = device.workspace_for("scint_slow_ft", nt, nf)
     fs_t = device.to_device(fscale, torch.float64)
     out = torch.empty((nt, nf), dtype=torch.complex128, device=dev)
-    _lib.check(lib.scint_slow_ft(device.ptr(dyn_t), nt, nf, device.ptr(fs_t), device.ptr(out), device.ptr(ws), ws.numel(),
-                                 device.stream_ptr()), "scint_slow_ft")
+    _lib.call("scint_slow_ft", dyn_t, nt, nf, fs_t, out, ws, ws.numel(), device.stream_ptr())
     return out if out_device else out.cpu().numpy()

@@ -42,6 +42,7 @@ There is no CPU fallback: without the HIP library or without a GPU every
 function raises ``ScintHipError``.
 """
 import ctypes
+import types
 import warnings
 
 import numpy as np
@@ -51,7 +52,7 @@ from scipy.optimize import curve_fit, minimize
 from . import _lib, units
 from . import device as _dv
 from .clean import svd_model  # noqa: F401  (ththmod.py:18-35, on the kernels of correct_dyn: csrc/clean.hpp)
-from .device import empty, ptr, require_gpu, stream_ptr, workspace
+from .device import empty, require_gpu, stream_ptr, workspace, workspace_for
 
 DEFAULT_TOL = 1e-12       # Ritz-residual tolerance of the Lanczos eigen-solver
 DEFAULT_MAX_ITER = 300    # Lanczos steps (ARPACK needs 30-50 restarts-equivalent mat-vecs)
@@ -200,15 +201,12 @@ def _eta_float(eta):
 # ----------------------------------------------------------------------------
 def _thth_dev(cs_t, grid, eta, keep_idx, hermetian):
     require_gpu()
-    lib = _lib.load()
     n = int(keep_idx.shape[0])
     out = empty((n, n), torch.complex128)
     if n == 0:
         return out
     keep_t = to_device(keep_idx, torch.int32)
-    rc = lib.scint_thth_map(ptr(cs_t), ctypes.byref(grid.geom), ptr(grid.th_dev()), grid.M,
-                            ptr(keep_t), n, eta, 1 if hermetian else 0, ptr(out), stream_ptr())
-    _lib.check(rc, "scint_thth_map")
+    _lib.call("scint_thth_map", cs_t, grid.geom, grid.th_dev(), grid.M, keep_t, n, eta, 1 if hermetian else 0, out, stream_ptr())
     return out
 
 
@@ -226,19 +224,14 @@ def _host_checked(arr, grid, hermetian):
 
 def _eigh_top_dev(a_t, v0_t=None, want_vec=True, tol=DEFAULT_TOL, max_iter=DEFAULT_MAX_ITER):
     """Top ('LA') eigenpair of a Hermitian device matrix.  Returns (w float, V tensor|None, iters)."""
-    lib = _lib.load()
     n = int(a_t.shape[0])
     if n < 2:
         raise ValueError("eigen-decomposition needs at least a 2x2 theta-theta matrix")
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_eigh_top_workspace_bytes(n, max_iter, ctypes.byref(need)), "eigh_top_workspace_bytes")
-    ws = workspace.get(need.value)
+    ws = workspace_for("scint_eigh_top", n, max_iter)
     w_t = empty((1,), torch.float64)
     st_t = torch.zeros((2,), dtype=torch.int32, device=a_t.device)
     vec_t = empty((n,), torch.complex128) if want_vec else None
-    rc = lib.scint_eigh_top(ptr(a_t), n, ptr(v0_t), tol, max_iter, ptr(w_t), ptr(vec_t),
-                            ptr(st_t[0:1]), ptr(st_t[1:2]), ptr(ws), ws.numel(), stream_ptr())
-    _lib.check(rc, "scint_eigh_top")
+    _lib.call("scint_eigh_top", a_t, n, v0_t, tol, max_iter, w_t, vec_t, st_t[0:1], st_t[1:2], ws, ws.numel(), stream_ptr())
     status, iters = (int(v) for v in st_t.cpu())
     if status != _lib.SCINT_OK:
         raise ArithmeticError(f"top-eigenpair iteration failed (status {status}, {iters} steps)")
@@ -248,28 +241,21 @@ def _eigh_top_dev(a_t, v0_t=None, want_vec=True, tol=DEFAULT_TOL, max_iter=DEFAU
 def _rev_map_dev(grid_geom, th_t, n, eta, hermetian, thth_t=None, vec_t=None, w_t=None, info=None):
     """`info` (a dict, tests): receives `uniform_grid` -- word 9 of the call's scratch, 1 when the rank-1 Hermitian image was
     formed by the uniform-grid kernel (csrc/thth.hip: rev_diag_kernel), 0 when by the general one."""
-    lib = _lib.load()
     recov = empty((grid_geom.ntau, grid_geom.nfd), torch.complex128)
     rank1 = thth_t is None
     scratch = empty((256,), torch.uint8)       # its own buffer: `workspace` may be live in a caller
-    rc = lib.scint_rev_map(ptr(thth_t), ptr(vec_t), ptr(w_t), 1 if rank1 else 0, ptr(th_t), n,
-                           ctypes.byref(grid_geom), eta, 1 if hermetian else 0, ptr(recov),
-                           ptr(scratch), scratch.numel(), stream_ptr())
-    _lib.check(rc, "scint_rev_map")
+    _lib.call("scint_rev_map", thth_t, vec_t, w_t, 1 if rank1 else 0, th_t, n, grid_geom, eta, 1 if hermetian else 0, recov,
+              scratch, scratch.numel(), stream_ptr())
     if info is not None:
         info["uniform_grid"] = int(scratch.cpu().numpy().view(np.uint64)[9])
     return recov
 
 
 def _model_dev(recov_t):
-    lib = _lib.load()
     ntau, nfd = (int(v) for v in recov_t.shape)
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_model_workspace_bytes(ntau, nfd, ctypes.byref(need)), "model_workspace_bytes")
-    ws = workspace.get(need.value)
+    ws = workspace_for("scint_model", ntau, nfd)
     model = empty((ntau, nfd), torch.float64)
-    rc = lib.scint_model_from_recov(ptr(recov_t), ntau, nfd, ptr(model), ptr(ws), ws.numel(), stream_ptr())
-    _lib.check(rc, "scint_model_from_recov")
+    _lib.call("scint_model_from_recov", recov_t, ntau, nfd, model, ws, ws.numel(), stream_ptr())
     return model
 
 
@@ -343,7 +329,6 @@ def modeler(CS, tau, fd, eta, edges, hermetian=True):
 
 def chisq_calc(dspec, CS, tau, fd, eta, edges, N, mask=None):
     """chi**2 of the theta-theta model dynamic spectrum (ththmod.py:330-368)."""
-    lib = _lib.load()
     grid = _Grid(tau, fd, edges)
     cs_t = _cs_dev(CS, grid)
     _, _, _, _, model_t, _ = _modeler_dev(cs_t, grid, _eta_float(eta))
@@ -351,9 +336,7 @@ def chisq_calc(dspec, CS, tau, fd, eta, edges, N, mask=None):
     nf, nt = (int(v) for v in d_t.shape)
     m_t = None if mask is None else to_device(np.asarray(mask, dtype=np.uint8), torch.uint8)
     out = empty((1,), torch.float64)
-    rc = lib.scint_chisq(ptr(model_t), int(model_t.shape[1]), ptr(d_t), nf, nt, ptr(m_t), float(N),
-                         ptr(out), stream_ptr())
-    _lib.check(rc, "scint_chisq")
+    _lib.call("scint_chisq", model_t, int(model_t.shape[1]), d_t, nf, nt, m_t, N, out, stream_ptr())
     return float(out.cpu()[0])
 
 
@@ -373,10 +356,9 @@ def default_batch(nmax, neta, eigenvalues_only=True):
                                      chunks around the certificate pass; 2400 eta/s, round 5 call 1)
       mixed-all eigenPAIR sweeps     138 slots                                                                 -> 3726"""
     nb = -(-nmax // 64)
-    lib = _lib.load()
-    mode = lib.scint_sweep_precision(-1)
+    mode = _lib.call("scint_sweep_precision", -1)
     use32 = mode == 2 or (eigenvalues_only and mode == 1)
-    wg = max(1, int(lib.scint_sweep_workgroups(nb, 1 if use32 else 0)))
+    wg = max(1, _lib.call("scint_sweep_workgroups", nb, 1 if use32 else 0))
     if use32:
         target = 5778 if eigenvalues_only else 3726
     else:
@@ -403,11 +385,32 @@ def sweep_precision(mode=None):
     What it buys is HBM bytes: 1.6x the sweep rate at N = 4095 on one MI355X.  Sweeps of small matrices
     (the 64 x 150 chunks of the tutorial data: N ~ 100) are bound by launch latency, not bytes, and a curvature spends
     two to three extra chunks of passes around its certificate: leave those in ``"f64"``."""
-    lib = _lib.load()
     codes = {None: -1, "f64": 0, "mixed": 1, "mixed-all": 2}
     if mode not in codes:
         raise ValueError("sweep_precision: mode must be 'f64', 'mixed', 'mixed-all' or None")
-    return {0: "f64", 1: "mixed", 2: "mixed-all"}[lib.scint_sweep_precision(codes[mode])]
+    return {0: "f64", 1: "mixed", 2: "mixed-all"}[_lib.call("scint_sweep_precision", codes[mode])]
+
+
+def _sweep_open(CS, tau, fd, etas, edges):
+    """What every single-chunk sweep starts with: (grid, conjugate spectrum on the device, curvatures as a float64 array)."""
+    grid = _Grid(tau, fd, edges)
+    _check_sweep_cs(grid.geom.ntau, grid.geom.nfd)
+    cs_t = _cs_dev(CS, grid)
+    etas_v = np.ascontiguousarray(np.atleast_1d(units.strip(etas, "etas", "s3", warn=False)).astype(float))
+    return grid, cs_t, etas_v
+
+
+def _sweep_results(val_t, st_t):
+    """What every sweep ends with: (values[neta] on the host, NaN where the curvature's status is not 0; st[2, neta] = status,
+    Lanczos steps)."""
+    val = val_t.cpu().numpy()
+    st = st_t.cpu().numpy()
+    val[st[0] != 0] = np.nan
+    return val, st
+
+
+def _split_chunks(val, bounds):
+    return [val[bounds[i]:bounds[i + 1]] for i in range(len(bounds) - 1)]
 
 
 def eval_sweep(CS, tau, fd, etas, edges, tol=DEFAULT_TOL, max_iter=DEFAULT_MAX_ITER, batch=None,
@@ -417,32 +420,18 @@ def eval_sweep(CS, tau, fd, etas, edges, tol=DEFAULT_TOL, max_iter=DEFAULT_MAX_I
 
     Failed curvatures are NaN, as in the reference.  With `return_info` also
     returns a dict with per-eta matrix sizes N, Lanczos steps and status."""
-    lib = _lib.load()
-    grid = _Grid(tau, fd, edges)
-    _check_sweep_cs(grid.geom.ntau, grid.geom.nfd)
-    cs_t = _cs_dev(CS, grid)
-    etas_v = np.atleast_1d(units.strip(etas, "etas", "s3", warn=False)).astype(float)
+    grid, cs_t, etas_v = _sweep_open(CS, tau, fd, etas, edges)
     neta, M = etas_v.shape[0], grid.M
     keep_t, keep_n = _sweep_inputs_dev(grid, etas_v)
     nmax = max(int(keep_n.max()), 1)
     if batch is None:
         batch = default_batch(nmax, neta)
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_eval_sweep_workspace_bytes(M, neta, batch, max_iter, ctypes.byref(need)),
-               "eval_sweep_workspace_bytes")
-    ws = workspace.get(need.value)
+    ws = workspace_for("scint_eval_sweep", M, neta, batch, max_iter)
     eigs_t = empty((neta,), torch.float64)
     st_t = empty((2, neta), torch.int32)              # status / step counts: initialised inside the library
-    etas_c = np.ascontiguousarray(etas_v)
-    rc = lib.scint_eval_sweep(ptr(cs_t), ctypes.byref(grid.geom), ptr(grid.th_dev()), M, ptr(keep_t),
-                              keep_n.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                              etas_c.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), neta,
-                              tol, max_iter, batch, ptr(eigs_t), ptr(st_t[0]), ptr(st_t[1]),
-                              ptr(ws), ws.numel(), stream_ptr())
-    _lib.check(rc, "scint_eval_sweep")
-    eigs = eigs_t.cpu().numpy()
-    st = st_t.cpu().numpy()
-    eigs[st[0] != 0] = np.nan            # failures -> NaN (ththmod.py:795-799)
+    _lib.call("scint_eval_sweep", cs_t, grid.geom, grid.th_dev(), M, keep_t, keep_n, etas_v, neta, tol, max_iter, batch,
+              eigs_t, st_t[0], st_t[1], ws, ws.numel(), stream_ptr())
+    eigs, st = _sweep_results(eigs_t, st_t)           # failures -> NaN (ththmod.py:795-799)
     if return_info:
         return eigs, {"N": keep_n.copy(), "iters": st[1].copy(), "status": st[0].copy(), "batch": batch}
     return eigs
@@ -586,14 +575,11 @@ def _sweep_inputs_dev(grid, etas_v):
     keep_idx as a device tensor [neta, M], keep_n on the host.  For the eigenvalue sweep, whose host side needs
     only the counts -- the Python loop of :func:`_sweep_inputs` and the 4 MB upload of its table were 3 % of a
     4096^2 / 256-eta step."""
-    lib = _lib.load()
     neta, M = etas_v.shape[0], grid.M
     keep_t = empty((neta, M), torch.int32)
     n_t = empty((neta,), torch.int32)
-    etas_c = np.ascontiguousarray(etas_v, dtype=np.float64)
-    _lib.check(lib.scint_sweep_keep(ptr(grid.th_dev()), M, etas_c.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), neta,
-                                    float(grid.geom.tau_max), float(grid.geom.fd_max / 2), ptr(keep_t), ptr(n_t),
-                                    stream_ptr()), "scint_sweep_keep")
+    _lib.call("scint_sweep_keep", grid.th_dev(), M, np.ascontiguousarray(etas_v, dtype=np.float64), neta, grid.geom.tau_max,
+              grid.geom.fd_max / 2, keep_t, n_t, stream_ptr())
     return keep_t, n_t.cpu().numpy()
 
 
@@ -603,34 +589,20 @@ def eigvec_sweep(CS, tau, fd, etas, edges, tol=DEFAULT_TOL, max_iter=DEFAULT_MAX
 
     Returns (w[neta] float64 signed, V device tensor [neta, M] complex128 -- row i holds
     N_i = len(keep_i) entries, unit norm, arbitrary phase --, info dict)."""
-    lib = _lib.load()
-    grid = _Grid(tau, fd, edges)
-    _check_sweep_cs(grid.geom.ntau, grid.geom.nfd)
-    cs_t = _cs_dev(CS, grid)
-    etas_v = np.atleast_1d(units.strip(etas, "etas", "s3", warn=False)).astype(float)
+    grid, cs_t, etas_v = _sweep_open(CS, tau, fd, etas, edges)
     neta, M = etas_v.shape[0], grid.M
     keep_idx, keep_n = _sweep_inputs(grid, etas_v)
     nmax = max(int(keep_n.max()), 1)
     if batch is None:
         batch = default_batch(nmax, neta, eigenvalues_only=False)
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_eigvec_sweep_workspace_bytes(M, neta, batch, max_iter, ctypes.byref(need)),
-               "eigvec_sweep_workspace_bytes")
-    ws = workspace.get(need.value)
+    ws = workspace_for("scint_eigvec_sweep", M, neta, batch, max_iter)
     keep_t = _dv.to_device(keep_idx, torch.int32)
     w_t = empty((neta,), torch.float64)
     V_t = empty((neta, M), torch.complex128)          # zeroed (rows are N_i entries long) and filled inside the library
     st_t = empty((2, neta), torch.int32)              # status / step counts: initialised inside the library
-    etas_c = np.ascontiguousarray(etas_v)
-    rc = lib.scint_eigvec_sweep(ptr(cs_t), ctypes.byref(grid.geom), ptr(grid.th_dev()), M, ptr(keep_t),
-                                keep_n.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                etas_c.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), neta,
-                                tol, max_iter, batch, ptr(w_t), ptr(V_t), M, ptr(st_t[0]), ptr(st_t[1]),
-                                ptr(ws), ws.numel(), stream_ptr())
-    _lib.check(rc, "scint_eigvec_sweep")
-    st = st_t.cpu().numpy()
-    w = w_t.cpu().numpy()
-    w[st[0] != 0] = np.nan
+    _lib.call("scint_eigvec_sweep", cs_t, grid.geom, grid.th_dev(), M, keep_t, keep_n, etas_v, neta, tol, max_iter, batch,
+              w_t, V_t, M, st_t[0], st_t[1], ws, ws.numel(), stream_ptr())
+    w, st = _sweep_results(w_t, st_t)
     info = {"N": keep_n.copy(), "iters": st[1].copy(), "status": st[0].copy(), "batch": batch,
             "keep_idx": keep_idx, "w_dev": w_t}
     return w, V_t, info
@@ -645,11 +617,7 @@ def chisq_sweep(dspec, CS, tau, fd, etas, edges, N, mask=None, return_info=False
     back-map, inverse FFT and chi**2 reduction are chained on a side stream while the sweep goes
     on -- no per-eta round trip through Python.  ``share_walk`` (default): curvatures that keep the same theta centres
     share the partner table of their back-maps (same pairs, same sums: not a bit changes; False exists for the test of that)."""
-    lib = _lib.load()
-    grid = _Grid(tau, fd, edges)
-    _check_sweep_cs(grid.geom.ntau, grid.geom.nfd)
-    cs_t = _cs_dev(CS, grid)
-    etas_v = np.ascontiguousarray(np.atleast_1d(units.strip(etas, "etas", "s3", warn=False)).astype(float))
+    grid, cs_t, etas_v = _sweep_open(CS, tau, fd, etas, edges)
     neta, M = etas_v.shape[0], grid.M
     # crop tables: when the crops are index ranges of sorted centres (always on the grids of the path) the [neta, M] index table is
     # built on the device and the reduced centres from the ranges alone (round 5: the host tables were 2.8 ms of a 290-ms step)
@@ -684,21 +652,13 @@ def chisq_sweep(dspec, CS, tau, fd, etas, edges, N, mask=None, return_info=False
     crop_group = np.ascontiguousarray(crop_group, dtype=np.int32)
     keep_n = np.ascontiguousarray(keep_n, dtype=np.int32)
     th_red_t = _dv.to_device(th_red, torch.float64)
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_chisq_sweep_workspace_bytes(M, neta, batch, max_iter, grid.geom.ntau, grid.geom.nfd, nf, nt,
-                                                     ctypes.byref(need)), "chisq_sweep_workspace_bytes")
-    ws = workspace.get(need.value)
+    ws = workspace_for("scint_chisq_sweep", M, neta, batch, max_iter, grid.geom.ntau, grid.geom.nfd, nf, nt)
     out = empty((neta,), torch.float64)               # NaN-initialised inside the library
     w_t = empty((neta,), torch.float64)
     V_t = empty((neta, M), torch.complex128)          # zeroed (rows are N_i entries long) and filled inside the library
     st_t = empty((2, neta), torch.int32)
-    rc = lib.scint_chisq_sweep(ptr(cs_t), ctypes.byref(grid.geom), ptr(grid.th_dev()), M, ptr(keep_t),
-                               keep_n.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                               etas_v.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), neta, tol, max_iter, batch,
-                               ptr(th_red_t), crop_group.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ptr(d_t), nf, nt, ptr(m_t),
-                               float(N), ptr(out), ptr(w_t), ptr(V_t), M,
-                               ptr(st_t[0]), ptr(st_t[1]), ptr(ws), ws.numel(), stream_ptr())
-    _lib.check(rc, "scint_chisq_sweep")
+    _lib.call("scint_chisq_sweep", cs_t, grid.geom, grid.th_dev(), M, keep_t, keep_n, etas_v, neta, tol, max_iter, batch,
+              th_red_t, crop_group, d_t, nf, nt, m_t, N, out, w_t, V_t, M, st_t[0], st_t[1], ws, ws.numel(), stream_ptr())
     st = st_t.cpu().numpy()
     chis = out.cpu().numpy()
     chis[(st[0] != 0) | (keep_n < 3)] = np.nan   # failed curvatures (the reference's loop would raise there)
@@ -706,7 +666,7 @@ def chisq_sweep(dspec, CS, tau, fd, etas, edges, N, mask=None, return_info=False
         w = w_t.cpu().numpy()
         w[(st[0] != 0) | (keep_n < 3)] = np.nan      # as chis: no model exists for these curvatures
         fused, redone = ctypes.c_int32(), ctypes.c_int64()
-        _lib.check(lib.scint_chisq_sweep_last_route(ctypes.byref(fused), ctypes.byref(redone)), "scint_chisq_sweep_last_route")
+        _lib.call("scint_chisq_sweep_last_route", fused, redone)
         return chis, {"w": w, "N": keep_n.copy(), "iters": st[1].copy(), "status": st[0].copy(), "batch": batch,
                       "fused": bool(fused.value), "redone": int(redone.value)}
     return chis
@@ -725,7 +685,6 @@ def _multi_keep_dev(G, etas_all, th_stack):
     (each chunk has its own theta centres and axes), and the counts on the host after ONE read-back.  Round 5: the host loop
     of :func:`_sweep_inputs` over 256 chunks and the upload of its 171-MB table were a tenth of a ``fit_thetatheta`` of a 4096^2
     observation (bench.py --workload fit_thetatheta)."""
-    lib = _lib.load()
     M = G[0].M
     # (round 6) chunks that share their grid OBJECT and their curvatures (the chunks of one frequency row of the phase retrieval, where
     # chunk_retrieval_batch makes one grid per row) share their table: one call per distinct (grid, curvatures), rows expanded on the device
@@ -744,11 +703,9 @@ def _multi_keep_dev(G, etas_all, th_stack):
         ne = int(et.shape[0])
         if ne == 0:
             continue
-        et_c = np.ascontiguousarray(et, dtype=np.float64)
         o = off_u[c]
-        _lib.check(lib.scint_sweep_keep(th_stack[c].data_ptr(), M, et_c.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ne,
-                                        float(g.geom.tau_max), float(g.geom.fd_max / 2), keep_u[o:o + ne].data_ptr(),
-                                        n_u[o:o + ne].data_ptr(), stream_ptr()), "scint_sweep_keep")
+        _lib.call("scint_sweep_keep", th_stack[c], M, np.ascontiguousarray(et, dtype=np.float64), ne, g.geom.tau_max,
+                  g.geom.fd_max / 2, keep_u[o:o + ne], n_u[o:o + ne], stream_ptr())
     n_host = np.ascontiguousarray(n_u.cpu().numpy(), dtype=np.int32)
     if len(uniq) == len(G):
         return keep_u[:off], n_host[:off]
@@ -756,6 +713,30 @@ def _multi_keep_dev(G, etas_all, th_stack):
         if len(G) else np.zeros(0, dtype=np.int64)
     keep_t = keep_u.index_select(0, _dv.to_device(rows, torch.int64))
     return keep_t, np.ascontiguousarray(n_host[rows], dtype=np.int32)
+
+
+def _multi_sweep_inputs(cs_stack, grids, etas_list):
+    """What the sweeps over MANY chunks start with: the grids as ``_Grid``s, the stack checked against them, the curvatures of
+    all chunks in one array (``etas_v``; chunk c owns ``bounds[c]:bounds[c + 1]``, ``cs_idx`` names each curvature's spectrum), the
+    geometry array and the theta centres of every chunk, and the crop tables (``keep_t`` on the device, ``keep_cnt`` on the host)."""
+    G = [g if isinstance(g, _Grid) else _Grid(*g) for g in grids]
+    ncs = len(G)
+    cs_t = _dv.to_device(cs_stack, torch.complex128)
+    if cs_t.dim() != 3 or cs_t.shape[0] != ncs:
+        raise ValueError("cs_stack must be [nchunk, ntau, nfd] with one spectrum per grid")
+    M = G[0].M
+    if any(g.M != M or (g.geom.ntau, g.geom.nfd) != tuple(cs_t.shape[1:]) for g in G):
+        raise ValueError("all chunks must share the CS shape and the number of edges")
+    _check_sweep_cs(G[0].geom.ntau, G[0].geom.nfd)
+    etas_all = [np.atleast_1d(units.strip(et, "etas", "s3", warn=False)).astype(float) for _, et in zip(G, etas_list)]
+    etas_v = np.ascontiguousarray(np.concatenate(etas_all))
+    cs_idx = np.ascontiguousarray(np.concatenate([np.full(et.shape[0], c, dtype=np.int32) for c, et in enumerate(etas_all)]))
+    th_stack = _dv.to_device(np.stack([g.th_cents for g in G]), torch.float64)
+    keep_t, keep_cnt = _multi_keep_dev(G, etas_all, th_stack)
+    return types.SimpleNamespace(G=G, ncs=ncs, cs_t=cs_t, cs_stride=int(cs_t.shape[1] * cs_t.shape[2]), M=M, etas_all=etas_all,
+                                 etas_v=etas_v, cs_idx=cs_idx, neta=etas_v.shape[0], th_stack=th_stack,
+                                 geoms=(_lib.CsGeom * ncs)(*[g.geom for g in G]), keep_t=keep_t, keep_cnt=keep_cnt,
+                                 bounds=np.cumsum([0] + [e.shape[0] for e in etas_all]))
 
 
 def eval_sweep_multi(cs_stack, grids, etas_list, tol=DEFAULT_TOL, max_iter=DEFAULT_MAX_ITER, batch=None,
@@ -766,50 +747,18 @@ def eval_sweep_multi(cs_stack, grids, etas_list, tol=DEFAULT_TOL, max_iter=DEFAU
     cs_stack: CUDA complex128 tensor [nchunk, ntau, nfd]; grids: one (tau, fd, edges) triple per
     chunk (all conjugate spectra one shape, all edges one length); etas_list: per-chunk eta
     arrays.  Returns a list of eigenvalue arrays (NaN where a curvature failed)."""
-    lib = _lib.load()
-    G = [g if isinstance(g, _Grid) else _Grid(*g) for g in grids]
-    ncs = len(G)
-    cs_t = _dv.to_device(cs_stack, torch.complex128)
-    if cs_t.dim() != 3 or cs_t.shape[0] != ncs:
-        raise ValueError("cs_stack must be [nchunk, ntau, nfd] with one spectrum per grid")
-    M = G[0].M
-    if any(g.M != M or (g.geom.ntau, g.geom.nfd) != tuple(cs_t.shape[1:]) for g in G):
-        raise ValueError("all chunks must share the CS shape and the number of edges")
-    _check_sweep_cs(G[0].geom.ntau, G[0].geom.nfd)
-    etas_all, cs_index = [], []
-    for c, (g, et) in enumerate(zip(G, etas_list)):
-        et = np.atleast_1d(units.strip(et, "etas", "s3", warn=False)).astype(float)
-        etas_all.append(et)
-        cs_index.append(np.full(et.shape[0], c, dtype=np.int32))
-    etas_v = np.ascontiguousarray(np.concatenate(etas_all))
-    cs_idx = np.ascontiguousarray(np.concatenate(cs_index))
-    neta = etas_v.shape[0]
-    geoms = (_lib.CsGeom * ncs)(*[g.geom for g in G])
-    th_stack = _dv.to_device(np.stack([g.th_cents for g in G]), torch.float64)
-    keep_t, keep_cnt = _multi_keep_dev(G, etas_all, th_stack)
+    s = _multi_sweep_inputs(cs_stack, grids, etas_list)
     if batch is None:
-        batch = default_batch(max(int(keep_cnt.max()), 1), neta)
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_eval_sweep_multi_workspace_bytes(M, neta, batch, max_iter, ncs, ctypes.byref(need)),
-               "eval_sweep_multi_workspace_bytes")
-    ws = workspace.get(need.value)
-    eigs_t = empty((neta,), torch.float64)
-    st_t = empty((2, neta), torch.int32)
-    rc = lib.scint_eval_sweep_multi(ptr(cs_t), ncs, int(cs_t.shape[1] * cs_t.shape[2]),
-                                    cs_idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), geoms,
-                                    ptr(th_stack), M, ptr(keep_t),
-                                    keep_cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                    etas_v.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), neta,
-                                    tol, max_iter, batch, ptr(eigs_t), ptr(st_t[0]), ptr(st_t[1]),
-                                    ptr(ws), ws.numel(), stream_ptr())
-    _lib.check(rc, "scint_eval_sweep_multi")
-    eigs = eigs_t.cpu().numpy()
-    st = st_t.cpu().numpy()
-    eigs[st[0] != 0] = np.nan
-    bounds = np.cumsum([0] + [e.shape[0] for e in etas_all])
-    out = [eigs[bounds[i]:bounds[i + 1]] for i in range(ncs)]
+        batch = default_batch(max(int(s.keep_cnt.max()), 1), s.neta)
+    ws = workspace_for("scint_eval_sweep_multi", s.M, s.neta, batch, max_iter, s.ncs)
+    eigs_t = empty((s.neta,), torch.float64)
+    st_t = empty((2, s.neta), torch.int32)
+    _lib.call("scint_eval_sweep_multi", s.cs_t, s.ncs, s.cs_stride, s.cs_idx, s.geoms, s.th_stack, s.M, s.keep_t, s.keep_cnt,
+              s.etas_v, s.neta, tol, max_iter, batch, eigs_t, st_t[0], st_t[1], ws, ws.numel(), stream_ptr())
+    eigs, st = _sweep_results(eigs_t, st_t)
+    out = _split_chunks(eigs, s.bounds)
     if return_info:
-        return out, {"N": keep_cnt, "iters": st[1], "status": st[0], "batch": batch}
+        return out, {"N": s.keep_cnt, "iters": st[1], "status": st[0], "batch": batch}
     return out
 
 
@@ -820,31 +769,12 @@ def eigvec_sweep_multi(cs_stack, grids, etas_list, tol=DEFAULT_TOL, max_iter=DEF
 
     Arguments as :func:`eval_sweep_multi`.  Returns (w list of float64 arrays, V device tensor
     [n_total, M] complex128 in chunk order, keep list of index arrays per (chunk, eta), info)."""
-    lib = _lib.load()
-    G = [g if isinstance(g, _Grid) else _Grid(*g) for g in grids]
-    ncs = len(G)
-    cs_t = _dv.to_device(cs_stack, torch.complex128)
-    if cs_t.dim() != 3 or cs_t.shape[0] != ncs:
-        raise ValueError("cs_stack must be [nchunk, ntau, nfd] with one spectrum per grid")
-    M = G[0].M
-    if any(g.M != M or (g.geom.ntau, g.geom.nfd) != tuple(cs_t.shape[1:]) for g in G):
-        raise ValueError("all chunks must share the CS shape and the number of edges")
-    _check_sweep_cs(G[0].geom.ntau, G[0].geom.nfd)
-    etas_all, cs_index = [], []
-    for c, (g, et) in enumerate(zip(G, etas_list)):
-        et = np.atleast_1d(units.strip(et, "etas", "s3", warn=False)).astype(float)
-        etas_all.append(et)
-        cs_index.append(np.full(et.shape[0], c, dtype=np.int32))
-    etas_v = np.ascontiguousarray(np.concatenate(etas_all))
-    cs_idx = np.ascontiguousarray(np.concatenate(cs_index))
-    neta = etas_v.shape[0]
-    geoms = (_lib.CsGeom * ncs)(*[g.geom for g in G])
-    th_stack = _dv.to_device(np.stack([g.th_cents for g in G]), torch.float64)
-    keep_t, keep_cnt = _multi_keep_dev(G, etas_all, th_stack)
+    s = _multi_sweep_inputs(cs_stack, grids, etas_list)
+    keep_t, keep_cnt = s.keep_t, s.keep_cnt
     # the callers want the kept indices on the host too: from the crop RANGES where the crops are ranges (sorted centres, eta >= 0:
     # the same expression at the bisection's probes), else from the device table
     keeps, rows_host, keep_cache = [], None, {}
-    for g, et in zip(G, etas_all):
+    for g, et in zip(s.G, s.etas_all):
         if et.shape[0] == 1:                       # (one curvature per chunk, the phase retrieval's case: the mask itself is cheaper than a bisection)
             kk = keep_cache.get((id(g), float(et[0])))
             if kk is None:
@@ -862,34 +792,21 @@ def eigvec_sweep_multi(cs_stack, grids, etas_list, tol=DEFAULT_TOL, max_iter=DEF
                     rows_host = keep_t.cpu().numpy()
                 keeps.append(rows_host[i, : keep_cnt[i]].copy())
     if batch is None:
-        batch = default_batch(max(int(keep_cnt.max()), 1), neta, eigenvalues_only=False)
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_eigvec_sweep_multi_workspace_bytes(M, neta, batch, max_iter, ncs, ctypes.byref(need)),
-               "eigvec_sweep_multi_workspace_bytes")
-    ws = workspace.get(need.value)
-    w_t = empty((neta,), torch.float64)
-    V_t = empty((neta, M), torch.complex128)
-    st_t = empty((2, neta), torch.int32)
-    rc = lib.scint_eigvec_sweep_multi(ptr(cs_t), ncs, int(cs_t.shape[1] * cs_t.shape[2]),
-                                      cs_idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), geoms,
-                                      ptr(th_stack), M, ptr(keep_t),
-                                      keep_cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                      etas_v.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), neta,
-                                      tol, max_iter, batch, ptr(w_t), ptr(V_t), M, ptr(st_t[0]), ptr(st_t[1]),
-                                      ptr(ws), ws.numel(), stream_ptr())
-    _lib.check(rc, "scint_eigvec_sweep_multi")
-    w = w_t.cpu().numpy()
-    st = st_t.cpu().numpy()
-    w[st[0] != 0] = np.nan
-    bounds = np.cumsum([0] + [e.shape[0] for e in etas_all])
-    return ([w[bounds[i]:bounds[i + 1]] for i in range(ncs)], V_t, keeps,
-            {"N": keep_cnt, "iters": st[1], "status": st[0], "batch": batch, "bounds": bounds})
+        batch = default_batch(max(int(keep_cnt.max()), 1), s.neta, eigenvalues_only=False)
+    ws = workspace_for("scint_eigvec_sweep_multi", s.M, s.neta, batch, max_iter, s.ncs)
+    w_t = empty((s.neta,), torch.float64)
+    V_t = empty((s.neta, s.M), torch.complex128)
+    st_t = empty((2, s.neta), torch.int32)
+    _lib.call("scint_eigvec_sweep_multi", s.cs_t, s.ncs, s.cs_stride, s.cs_idx, s.geoms, s.th_stack, s.M, keep_t, keep_cnt,
+              s.etas_v, s.neta, tol, max_iter, batch, w_t, V_t, s.M, st_t[0], st_t[1], ws, ws.numel(), stream_ptr())
+    w, st = _sweep_results(w_t, st_t)
+    return (_split_chunks(w, s.bounds), V_t, keeps,
+            {"N": keep_cnt, "iters": st[1], "status": st[0], "batch": batch, "bounds": s.bounds})
 
 
 def conjugate_spectrum(dspec, npad, tau=None, tau_mask=0.0, coher=True, pad_value=None, out=None):
     """Device conjugate spectrum of a chunk (ththmod.py:777-787): returns a CUDA
     complex128 tensor [(npad+1)*nf, (npad+1)*nt] (written into `out` when given)."""
-    lib = _lib.load()
     if pad_value is None and not isinstance(dspec, torch.Tensor):
         # the reference's own expression for the padding value, `dspec.mean()` in NumPy (ththmod.py:783), while the chunk is still
         # on the host: the same bits whether the chunk comes alone (single_search) or in a group's array (Dynspec._fit_chunks,
@@ -899,7 +816,7 @@ def conjugate_spectrum(dspec, npad, tau=None, tau_mask=0.0, coher=True, pad_valu
     nf, nt = (int(v) for v in d_t.shape)
     if pad_value is None:
         m = ctypes.c_double()
-        _lib.check(lib.scint_mean(ptr(d_t), nf * nt, ctypes.byref(m), stream_ptr()), "scint_mean")
+        _lib.call("scint_mean", d_t, nf * nt, m, stream_ptr())
         pad_value = m.value
     R = (npad + 1) * nf
     lo = hi = 0
@@ -910,15 +827,11 @@ def conjugate_spectrum(dspec, npad, tau=None, tau_mask=0.0, coher=True, pad_valu
             lo, hi = int(sel[0]), int(sel[-1]) + 1
             if hi - lo != sel.size:
                 raise ValueError("tau mask is not a contiguous block of delays")
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_cs_workspace_bytes(nf, nt, npad, ctypes.byref(need)), "cs_workspace_bytes")
-    ws = workspace.get(need.value)
+    ws = workspace_for("scint_cs", nf, nt, npad)
     cs_t = empty((R, (npad + 1) * nt), torch.complex128) if out is None else out
     if tuple(cs_t.shape) != (R, (npad + 1) * nt) or cs_t.dtype != torch.complex128 or not cs_t.is_contiguous():
         raise ValueError("conjugate_spectrum: `out` must be a contiguous complex128 tensor of the padded shape")
-    rc = lib.scint_cs(ptr(d_t), nf, nt, npad, float(pad_value), lo, hi, 0 if coher else 1,
-                      ptr(cs_t), ptr(ws), ws.numel(), stream_ptr())
-    _lib.check(rc, "scint_cs")
+    _lib.call("scint_cs", d_t, nf, nt, npad, pad_value, lo, hi, 0 if coher else 1, cs_t, ws, ws.numel(), stream_ptr())
     return cs_t
 
 
@@ -980,16 +893,11 @@ def single_search(params):
 # ----------------------------------------------------------------------------
 def _ifft2_shifted_dev(x_t, scale=1.0, crop=None):
     """scale * ifft2(ifftshift(x))[:crop[0], :crop[1]] on the device (complex128)."""
-    lib = _lib.load()
     rows, cols = (int(v) for v in x_t.shape)
     cr, cc = crop if crop is not None else (rows, cols)
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_fft2_workspace_bytes(rows, cols, ctypes.byref(need)), "fft2_workspace_bytes")
-    ws = workspace.get(need.value)
+    ws = workspace_for("scint_fft2", rows, cols)
     out = empty((cr, cc), torch.complex128)
-    rc = lib.scint_ifft2_shifted(ptr(x_t), rows, cols, float(scale), cr, cc, ptr(out), ptr(ws), ws.numel(),
-                                 stream_ptr())
-    _lib.check(rc, "scint_ifft2_shifted")
+    _lib.call("scint_ifft2_shifted", x_t, rows, cols, scale, cr, cc, out, ws, ws.numel(), stream_ptr())
     return out
 
 
@@ -1081,7 +989,6 @@ def chunk_retrieval_batch(chunks, npad, tauMask, verbose=False, group_bytes=None
             continue
         # (round 6) one call for the group's conjugate spectra, one for its back-maps and inverse transforms: a dozen Python-issued
         # launches per chunk were 0.17 s of a 0.31-s calc_wavefield of 961 chunks
-        lib = _lib.load()
         if dev_chunks is None:
             d_t = _dv.to_device(d_all[: len(live)], torch.float64)
         elif live == list(range(len(group))):
@@ -1097,12 +1004,8 @@ def chunk_retrieval_batch(chunks, npad, tauMask, verbose=False, group_bytes=None
                 if lohi[j, 1] - lohi[j, 0] != sel.size:
                     raise ValueError("tau mask is not a contiguous block of delays")
         pads_a = np.ascontiguousarray(pads, dtype=np.float64)
-        need = ctypes.c_size_t()
-        _lib.check(lib.scint_cs_workspace_bytes(nf, nt, npad, ctypes.byref(need)), "cs_workspace_bytes")
-        ws = workspace.get(need.value)
-        _lib.check(lib.scint_cs_batch(ptr(d_t), len(live), nf, nt, npad, pads_a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                      lohi.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), 0, ptr(stack), ptr(ws), ws.numel(), stream_ptr()),
-                   "scint_cs_batch")
+        ws = workspace_for("scint_cs", nf, nt, npad)
+        _lib.call("scint_cs_batch", d_t, len(live), nf, nt, npad, pads_a, lohi, 0, stack, ws, ws.numel(), stream_ptr())
         w_list, V_t, keeps, info = eigvec_sweep_multi(stack[: len(live)], grids, etas)
         V = V_t.cpu().numpy()
         M = grids[0].M
@@ -1149,7 +1052,6 @@ def _retrieval_tail_dev(rows, th_red, keep_n, class_id, grids, etas, nf, nt, out
     the pair counts of their back-maps (the caller's promise); None = the classes of equal (curvature, centres, axes).
     ``out_t``: device [n, nf, nt] complex128 the result is written into (chunks with keep_n < 2 keep what it holds); default
     zeros.  Returns the device tensor."""
-    lib = _lib.load()
     n, M = (int(v) for v in np.shape(rows))
     keep_n = np.ascontiguousarray(keep_n, dtype=np.int32)
     etas_a = np.ascontiguousarray(etas, dtype=np.float64)
@@ -1168,14 +1070,9 @@ def _retrieval_tail_dev(rows, th_red, keep_n, class_id, grids, etas, nf, nt, out
     if out_t is None:
         out_t = torch.zeros((n, nf, nt), dtype=torch.complex128, device=require_gpu())
     geoms = (_lib.CsGeom * n)(*[g_.geom for g_ in grids])
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_retrieval_tail_workspace_bytes(M, grids[0].geom.ntau, grids[0].geom.nfd, ctypes.byref(need)),
-               "retrieval_tail_workspace_bytes")
-    ws = workspace.get(need.value)
-    _lib.check(lib.scint_retrieval_tail(ptr(rows_t), ptr(th_t), keep_n.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                        class_id.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), geoms,
-                                        etas_a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n, M, nf, nt, nf * nt / 4,
-                                        ptr(out_t), ptr(ws), ws.numel(), stream_ptr()), "scint_retrieval_tail")
+    ws = workspace_for("scint_retrieval_tail", M, grids[0].geom.ntau, grids[0].geom.nfd)
+    _lib.call("scint_retrieval_tail", rows_t, th_t, keep_n, class_id, geoms, etas_a, n, M, nf, nt, nf * nt / 4, out_t,
+              ws, ws.numel(), stream_ptr())
     return out_t
 
 
@@ -1235,7 +1132,6 @@ def _vlbi_composites_dev(stack_t, slots, grids, etas, keeps, n_dish, S=None):
     spectra; slots: int [n, nspec], the slot of spectrum idx of chunk k (the reference's list order); grids / etas / keeps: per
     chunk its _Grid, curvature and the kept indices of thth_redmap's crop.  Returns the device tensor [n, S * S]: chunk k's dense
     [n_dish N_k, n_dish N_k] composite sits at the start of row k (S = n_dish max N_k unless given larger)."""
-    lib = _lib.load()
     n, M = len(grids), grids[0].M
     nspec = n_dish * (n_dish + 1) // 2
     slots = np.ascontiguousarray(slots, dtype=np.int64).reshape(n, nspec)
@@ -1255,13 +1151,9 @@ def _vlbi_composites_dev(stack_t, slots, grids, etas, keeps, n_dish, S=None):
     th_t, keep_t = _dv.to_device(th_all, torch.float64), _dv.to_device(keep_all, torch.int32)
     comp = torch.empty((n, S * S), dtype=torch.complex128, device=stack_t.device)
     geoms = (_lib.CsGeom * n)(*[g_.geom for g_ in grids])
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_vlbi_composite_workspace_bytes(n, n_dish, ctypes.byref(need)), "vlbi_composite_workspace_bytes")
-    ws = workspace.get(need.value)
-    _lib.check(lib.scint_vlbi_composite(ptr(stack_t), R * C, slots.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), geoms, ptr(th_t), M,
-                                        ptr(keep_t), keep_n.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                        etas.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n, n_dish, ptr(comp), S * S,
-                                        ptr(ws), ws.numel(), stream_ptr()), "scint_vlbi_composite")
+    ws = workspace_for("scint_vlbi_composite", n, n_dish)
+    _lib.call("scint_vlbi_composite", stack_t, R * C, slots, geoms, th_t, M, keep_t, keep_n, etas, n, n_dish, comp, S * S,
+              ws, ws.numel(), stream_ptr())
     return comp
 
 
@@ -1308,7 +1200,6 @@ def vlbi_retrieval_batch(chunks, npad, n_dish, tauMask, verbose=False, group_byt
     R, C = (npad + 1) * nf, (npad + 1) * nt
     _check_sweep_cs(R, C)
     dev = require_gpu()
-    lib = _lib.load()
     mask_us = float(units.strip(tauMask, "tauMask", "us", warn=False))
     out = torch.zeros((len(chunks), n_dish, nf, nt), dtype=torch.complex128, device=dev) if out_device else \
         np.zeros((len(chunks), n_dish, nf, nt), dtype=complex)
@@ -1369,20 +1260,15 @@ def vlbi_retrieval_batch(chunks, npad, n_dish, tauMask, verbose=False, group_byt
                 if lohi[j, 1] - lohi[j, 0] != sel.size:
                     raise ValueError("tau mask is not a contiguous block of delays")
         stack = torch.empty((n * nspec, R, C), dtype=torch.complex128, device=dev)   # slots: the dynamic spectra, then the visibilities
-        need = ctypes.c_size_t()
-        _lib.check(lib.scint_cs_workspace_bytes(nf, nt, npad, ctypes.byref(need)), "cs_workspace_bytes")
-        ws = workspace.get(need.value)
+        ws = workspace_for("scint_cs", nf, nt, npad)
         d_t = _dv.to_device(d_all, torch.float64)
         lohi_d = np.ascontiguousarray(np.repeat(lohi, n_dish, axis=0))
-        _lib.check(lib.scint_cs_batch(ptr(d_t), n * n_dish, nf, nt, npad, pads.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                      lohi_d.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), 0, ptr(stack), ptr(ws), ws.numel(),
-                                      stream_ptr()), "scint_cs_batch")
+        _lib.call("scint_cs_batch", d_t, n * n_dish, nf, nt, npad, pads, lohi_d, 0, stack, ws, ws.numel(), stream_ptr())
         v_t = None
         if nvis:
             v_t = _dv.to_device(v_all, torch.complex128)
             lohi_v = np.ascontiguousarray(np.repeat(lohi, nvis, axis=0))
-            _lib.check(lib.scint_cs_complex_batch(ptr(v_t), n * nvis, nf, nt, npad, lohi_v.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                                  ptr(stack[n * n_dish:]), ptr(ws), ws.numel(), stream_ptr()), "scint_cs_complex_batch")
+            _lib.call("scint_cs_complex_batch", v_t, n * nvis, nf, nt, npad, lohi_v, stack[n * n_dish:], ws, ws.numel(), stream_ptr())
         slots = np.empty((n, nspec), dtype=np.int64)
         for q, i in enumerate(dyn_idx):
             slots[:, i] = np.arange(n) * n_dish + q
@@ -1392,14 +1278,12 @@ def vlbi_retrieval_batch(chunks, npad, n_dish, tauMask, verbose=False, group_byt
         # dominant ('LA') eigenpair of every composite, started from the zero-theta row of the first station's block row
         sizes = np.ascontiguousarray(n_dish * keep_n, dtype=np.int32)
         start = np.ascontiguousarray(keep_n // 2, dtype=np.int32)
-        _lib.check(lib.scint_eigh_top_batch_workspace_bytes(S, max_iter, n, ctypes.byref(need)), "eigh_top_batch_workspace_bytes")
-        ws = workspace.get(need.value)
+        ws = workspace_for("scint_eigh_top_batch", S, max_iter, n)
         w_t = empty((n,), torch.float64)
         V_t = torch.zeros((n, S), dtype=torch.complex128, device=dev)
         st_t = torch.zeros((2, n), dtype=torch.int32, device=dev)
-        _lib.check(lib.scint_eigh_top_batch(ptr(comp), S * S, sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                            start.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n, tol, max_iter, ptr(w_t), ptr(V_t), S,
-                                            ptr(st_t[0]), ptr(st_t[1]), ptr(ws), ws.numel(), stream_ptr()), "scint_eigh_top_batch")
+        _lib.call("scint_eigh_top_batch", comp, S * S, sizes, start, n, tol, max_iter, w_t, V_t, S, st_t[0], st_t[1],
+                  ws, ws.numel(), stream_ptr())
         st = st_t.cpu().numpy()
         if (st[0] != 0).any():
             j = int(np.nonzero(st[0])[0][0])
@@ -1568,7 +1452,6 @@ def mosaic_device(chunks_t, angles=None):
     are NumPy's, and a second kernel adds ``chunk_new * mask * exp(1j * rot)``.  Bit-identical to the host loop on the same
     chunks (tests); the host loop spent 0.26 s on those 961 chunks and needed them on the host (1 GB).
     ``angles``: a float array [ncf * nct] that receives every chunk's rotation (the reference's ``rotInit`` is this very loop)."""
-    lib = _lib.load()
     ncf, nct, cwf, cwt = (int(v) for v in chunks_t.shape)
     rows, cols = _mosaic_tapers(ncf, nct, cwf, cwt)             # (raises for an odd size along an axis of several chunks)
     F, T = (ncf - 1) * (cwf // 2) + cwf, (nct - 1) * (cwt // 2) + cwt
@@ -1594,18 +1477,15 @@ def mosaic_device(chunks_t, angles=None):
                 table.append(((cf * (cwf // 2)) * T + ct * (cwt // 2), cf * nct + ct, 2 * (cf > 0) + (cf < ncf - 1), 2 * (ct > 0) + (ct < nct - 1)))
     jobs_t = _dv.to_device(np.asarray(table, dtype=np.int64), torch.int64)
     most = max(n for _, n in launches)
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_mosaic_workspace_bytes(cwf, cwt, most, ctypes.byref(need)), "mosaic_workspace_bytes")
-    ws = workspace.get(need.value)
+    ws = workspace_for("scint_mosaic", cwf, cwt, most)
     sums_t = empty((most, 2), torch.float64)
     count = cwf * cwt
     st = stream_ptr()
     chunks_c = chunks_t.contiguous()
     ph = np.empty((most, 2))
     for first, n in launches:
-        jp = jobs_t[first].data_ptr()
-        _lib.check(lib.scint_mosaic_phase(ptr(E_t), T, ptr(chunks_c), cwf, cwt, jp, n, ptr(rows_t), ptr(cols_t), fused,
-                                          ptr(ws), ws.numel(), ptr(sums_t), st), "scint_mosaic_phase")
+        jobs = jobs_t[first:first + n]
+        _lib.call("scint_mosaic_phase", E_t, T, chunks_c, cwf, cwt, jobs, n, rows_t, cols_t, fused, ws, ws.numel(), sums_t, st)
         sums = sums_t[:n].cpu().numpy()
         for k in range(n):
             tot = np.complex128(complex(sums[k, 0], sums[k, 1]))
@@ -1615,8 +1495,7 @@ def mosaic_device(chunks_t, angles=None):
             ph[k, 0], ph[k, 1] = e.real, e.imag
             if angles is not None:
                 angles[table[first + k][1]] = rot
-        _lib.check(lib.scint_mosaic_add(ptr(E_t), T, ptr(chunks_c), cwf, cwt, jp, n, ptr(rows_t), ptr(cols_t), fused,
-                                        ph.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), st), "scint_mosaic_add")
+        _lib.call("scint_mosaic_add", E_t, T, chunks_c, cwf, cwt, jobs, n, rows_t, cols_t, fused, ph, st)
     return E_t
 
 
@@ -1634,7 +1513,6 @@ class MosaicStack:
     Hessian need exactly the mosaic's shape and raise ``ValueError`` otherwise, as the NumPy broadcast there does."""
 
     def __init__(self, chunks, dspec=None, N=None):
-        self._lib = _lib.load()
         if isinstance(chunks, torch.Tensor):
             chunks_t = chunks.to(torch.complex128)
         else:
@@ -1654,7 +1532,7 @@ class MosaicStack:
             modes = (False, False)
         self._fused = 1 if modes[0] else 0
         need = ctypes.c_size_t()
-        _lib.check(self._lib.scint_mosaic_fit_workspace_bytes(self.ncf, self.nct, self.cwf, self.cwt, ctypes.byref(need)), "mosaic_fit_workspace_bytes")
+        _lib.call("scint_mosaic_fit_workspace_bytes", self.ncf, self.nct, self.cwf, self.cwt, need)
         self._ws_bytes = need.value
         self._W_t = None
         self._maps = [self._map(dspec), self._map(N)]
@@ -1717,11 +1595,8 @@ class MosaicStack:
             W_t = self._W_t
         out_t = empty((1 + 2 * self.n,), torch.float64) if want else None
         ws = workspace.get(self._ws_bytes) if want else None
-        _lib.check(self._lib.scint_mosaic_fit_eval(ptr(self.chunks_t), self.ncf, self.nct, self.cwf, self.cwt, ptr(self._rows_t), ptr(self._cols_t),
-                                                   ptr(coef_t), 1 if full else 0, self._fused, ptr(maps[0]) if maps[0] is not None else None,
-                                                   ptr(maps[1]) if maps[1] is not None else None, ptr(W_t), want,
-                                                   ptr(out_t) if want else None, ptr(ws) if want else None, ws.numel() if want else 0,
-                                                   stream_ptr()), "scint_mosaic_fit_eval")
+        _lib.call("scint_mosaic_fit_eval", self.chunks_t, self.ncf, self.nct, self.cwf, self.cwt, self._rows_t, self._cols_t, coef_t,
+                  1 if full else 0, self._fused, maps[0], maps[1], W_t, want, out_t, ws, ws.numel() if want else 0, stream_ptr())
         return W_t, (out_t.cpu().numpy() if want else None)
 
     def _mosaic(self, coef_t, full, out_device):
@@ -1773,9 +1648,8 @@ class MosaicStack:
         P = 2 * self.n - 1
         H_t = empty((P, P), torch.float64)
         ws = workspace.get(self._ws_bytes)
-        _lib.check(self._lib.scint_mosaic_fit_hess(ptr(self.chunks_t), self.ncf, self.nct, self.cwf, self.cwt, ptr(self._rows_t), ptr(self._cols_t),
-                                                   ptr(coef_t), ptr(maps[0]), ptr(maps[1]), ptr(W_t), ptr(H_t), ptr(ws), ws.numel(), stream_ptr()),
-                   "scint_mosaic_fit_hess")
+        _lib.call("scint_mosaic_fit_hess", self.chunks_t, self.ncf, self.nct, self.cwf, self.cwt, self._rows_t, self._cols_t, coef_t,
+                  maps[0], maps[1], W_t, H_t, ws, ws.numel(), stream_ptr())
         return H_t.cpu().numpy()
 
 
@@ -1852,7 +1726,6 @@ def chunk_cut_device(dyn_t, origins, cwf, cwt, fortran_order=False):
     order restated (csrc/mosaic.hip).  dyn_t: device [nf, nt] float64; origins: [(r0, c0)].  Returns (chunks [n, cwf, cwt], pads [n]).
     ``fortran_order``: the host array the reference would slice is Fortran-ordered (a transposed view: how psrflux files load) --
     ``np.copy`` keeps that order and NumPy's sums walk the window column by column; the means are then formed in that order."""
-    lib = _lib.load()
     nf, nt = (int(v) for v in dyn_t.shape)
     n = len(origins)
     o = np.asarray(origins, dtype=np.int32).reshape(n, 2)
@@ -1860,11 +1733,9 @@ def chunk_cut_device(dyn_t, origins, cwf, cwt, fortran_order=False):
         raise ValueError("chunk_cut_device: a window lies outside the dynamic spectrum")
     r0_t, c0_t = _dv.to_device(np.ascontiguousarray(o[:, 0]), torch.int32), _dv.to_device(np.ascontiguousarray(o[:, 1]), torch.int32)
     out_t, pad_t = empty((n, cwf, cwt), torch.float64), empty((n,), torch.float64)
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_mosaic_workspace_bytes(cwf, cwt, n, ctypes.byref(need)), "mosaic_workspace_bytes")
-    ws = workspace.get(need.value)
-    _lib.check(lib.scint_chunk_cut(ptr(dyn_t), nf, nt, ptr(r0_t), ptr(c0_t), n, cwf, cwt, 1 if fortran_order else 0, ptr(out_t), ptr(pad_t), ptr(ws), ws.numel(),
-                                   stream_ptr()), "scint_chunk_cut")
+    ws = workspace_for("scint_mosaic", cwf, cwt, n)
+    _lib.call("scint_chunk_cut", dyn_t, nf, nt, r0_t, c0_t, n, cwf, cwt, 1 if fortran_order else 0, out_t, pad_t, ws, ws.numel(),
+              stream_ptr())
     return out_t, pad_t
 
 
@@ -1872,7 +1743,7 @@ def gerchberg_saxton_device(wavefield, dyn, tau, niter=1):
     """Gerchberg-Saxton clean-up of a wavefield (Dynspec.gerchberg_saxton, dynspec.py:1858-1875):
     host normalisation + first amplitude projection, then `niter` device iterations of
     fft2 -> zero tau < 0 -> ifft2 -> amplitude projection.  Returns the new wavefield (NumPy)."""
-    lib = _lib.load()
+    _lib.load()
     wf = np.array(wavefield, dtype=complex)
     F, T = wf.shape
     d = np.asarray(dyn, dtype=float)[:F, :T]
@@ -1892,12 +1763,8 @@ def gerchberg_saxton_device(wavefield, dyn, tau, niter=1):
     wf_t = _dv.to_device(wf, torch.complex128)
     amp_t = _dv.to_device(amp, torch.float64)
     pos_t = _dv.to_device(posdspec.astype(np.uint8), torch.uint8)
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_gs_workspace_bytes(F, T, ctypes.byref(need)), "gs_workspace_bytes")
-    ws = workspace.get(need.value)
-    rc = lib.scint_gerchberg_saxton(ptr(wf_t), F, T, ptr(amp_t), ptr(pos_t), lo, hi, int(niter), ptr(ws),
-                                    ws.numel(), stream_ptr())
-    _lib.check(rc, "scint_gerchberg_saxton")
+    ws = workspace_for("scint_gs", F, T)
+    _lib.call("scint_gerchberg_saxton", wf_t, F, T, amp_t, pos_t, lo, hi, int(niter), ws, ws.numel(), stream_ptr())
     return wf_t.cpu().numpy()
 
 
@@ -2001,7 +1868,6 @@ def two_curve_map(CS, tau, fd, eta1, edges1, eta2, edges2):
     """Rectangular theta-theta for arclets of another curvature (ththmod.py:1557-1636): returns
     (thth_red[n2, n1], edges_red1, edges_red2) -- rows theta2 (edges2), columns theta1 (edges1) -- with the reference's index
     quirks (tau[1] / fd[1] origins, the negative-Doppler wrap, IndexError below -nfd)."""
-    lib = _lib.load()
     require_gpu()
     tau_v = units.strip(tau, "tau", "us", warn=False)
     fd_v = units.strip(fd, "fd", "mHz", warn=False)
@@ -2017,14 +1883,10 @@ def two_curve_map(CS, tau, fd, eta1, edges1, eta2, edges2):
     n2, n1 = int(rng[1]), int(rng[3])
     out = empty((max(n2, 1), max(n1, 1)), torch.complex128)
     flag = torch.zeros((1,), dtype=torch.int32, device=out.device)
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_two_curve_map_workspace_bytes(ctypes.byref(need)), "two_curve_map_workspace_bytes")
-    ws = workspace.get(need.value)
+    ws = workspace_for("scint_two_curve_map")
     th1_t, th2_t = to_device(th1, torch.float64), to_device(th2, torch.float64)
-    rc = lib.scint_two_curve_map(ptr(cs_t), ctypes.byref(geom), ptr(th1_t), th1.size, ptr(th2_t), th2.size, eta1_v, eta2_v,
-                                 rng.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _thin_check(geom, th1, th2),
-                                 ptr(out), ptr(flag), ptr(ws), ws.numel(), stream_ptr())
-    _lib.check(rc, "scint_two_curve_map")
+    _lib.call("scint_two_curve_map", cs_t, geom, th1_t, th1.size, th2_t, th2.size, eta1_v, eta2_v, rng, _thin_check(geom, th1, th2),
+              out, flag, ws, ws.numel(), stream_ptr())
     if int(flag.cpu()[0]):
         raise IndexError("two_curve_map: a Doppler index below -len(fd) (NumPy's fancy index raises here, ththmod.py:1612)")
     red = out[:n2, :n1].cpu().numpy()
@@ -2032,18 +1894,14 @@ def two_curve_map(CS, tau, fd, eta1, edges1, eta2, edges2):
 
 
 def _sv_run(cs_t, geoms, th1_stack, th2_stack, cs_index, ranges, checks, etas1, etas2, tol, max_iter, batch):
-    """scint_sv_sweep_multi on prepared inputs: (sv[neta], status[neta], iters[neta], batch)."""
-    lib = _lib.load()
+    """scint_sv_sweep_multi on prepared inputs: (sv[neta], NaN where the status is not 0; status[neta], iters[neta], batch)."""
     ncs, M1, M2 = len(geoms), int(th1_stack.shape[1]), int(th2_stack.shape[1])
     neta = int(etas1.shape[0])
     _check_sweep_cs(geoms[0].ntau, geoms[0].nfd)
     if batch is None:
         per = 16 * M1 * M2 + 96 * M1 + 16 * M1 * -(-M2 // max(4, -(-M2 // 256))) + 16 * max_iter + 4096
         batch = int(max(1, min(neta, 8192, DEFAULT_BATCH_BYTES // per)))
-    need = ctypes.c_size_t()
-    _lib.check(lib.scint_sv_sweep_multi_workspace_bytes(M1, M2, neta, batch, max_iter, ncs, ctypes.byref(need)),
-               "sv_sweep_multi_workspace_bytes")
-    ws = workspace.get(need.value)
+    ws = workspace_for("scint_sv_sweep_multi", M1, M2, neta, batch, max_iter, ncs)
     sv_t = empty((neta,), torch.float64)
     st_t = empty((2, neta), torch.int32)
     g_arr = (_lib.ThinGeom * ncs)(*geoms)
@@ -2052,15 +1910,10 @@ def _sv_run(cs_t, geoms, th1_stack, th2_stack, cs_index, ranges, checks, etas1, 
     ck = np.ascontiguousarray(checks, dtype=np.int32)
     e1 = np.ascontiguousarray(etas1, dtype=np.float64)
     e2 = np.ascontiguousarray(etas2, dtype=np.float64)
-    P = ctypes.POINTER
-    rc = lib.scint_sv_sweep_multi(ptr(cs_t), ncs, int(cs_t.shape[1] * cs_t.shape[2]), ci.ctypes.data_as(P(ctypes.c_int32)),
-                                  g_arr, ptr(th1_stack), M1, ptr(th2_stack), M2, rg.ctypes.data_as(P(ctypes.c_int32)),
-                                  ck.ctypes.data_as(P(ctypes.c_int32)), e1.ctypes.data_as(P(ctypes.c_double)),
-                                  e2.ctypes.data_as(P(ctypes.c_double)), neta, tol, max_iter, batch, ptr(sv_t),
-                                  ptr(st_t[0]), ptr(st_t[1]), ptr(ws), ws.numel(), stream_ptr())
-    _lib.check(rc, "scint_sv_sweep_multi")
-    st = st_t.cpu().numpy()
-    return sv_t.cpu().numpy(), st[0].copy(), st[1].copy(), batch
+    _lib.call("scint_sv_sweep_multi", cs_t, ncs, int(cs_t.shape[1] * cs_t.shape[2]), ci, g_arr, th1_stack, M1, th2_stack, M2,
+              rg, ck, e1, e2, neta, tol, max_iter, batch, sv_t, st_t[0], st_t[1], ws, ws.numel(), stream_ptr())
+    sv, st = _sweep_results(sv_t, st_t)       # NOCONV / EMPTY / NONFINITE / would-raise -> NaN (single_search_thin's except, :624-629)
+    return sv, st[0].copy(), st[1].copy(), batch
 
 
 def _thin_ranges(tau_max, edges1, edges2, etas, center_cut):
@@ -2131,9 +1984,7 @@ def sv_sweep_multi(cs_stack, grids, etas_list, center_cut=0.0, tol=DEFAULT_TOL, 
         th2_t = to_device(np.stack(th2s), torch.float64)
         sv, st, it, batch = _sv_run(cs_t, geoms, th1_t, th2_t, np.concatenate(cs_index), np.concatenate(ranges),
                                     np.concatenate(checks), etas_v, etas_v, tol, max_iter, batch)
-    sv[st != 0] = np.nan          # NOCONV / EMPTY / NONFINITE / would-raise -> NaN (single_search_thin's except, :624-629)
-    bounds = np.cumsum([0] + [e.shape[0] for e in etas_all])
-    out = [sv[bounds[i]:bounds[i + 1]] for i in range(ncs)]
+    out = _split_chunks(sv, np.cumsum([0] + [e.shape[0] for e in etas_all]))
     if return_info:
         return out, {"status": st, "iters": it, "ranges": np.concatenate(ranges), "batch": batch}
     return out

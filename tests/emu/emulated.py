@@ -24,12 +24,7 @@ def load():
     if _emu_lib is None:
         import build_emu
         from scintools_amd import _lib
-        lib = ctypes.CDLL(build_emu.build())
-        for name, (argtypes, restype) in _lib._SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes = argtypes
-            fn.restype = restype
-        _emu_lib = lib
+        _emu_lib = _lib.bind(ctypes.CDLL(build_emu.build()))
     return _emu_lib
 
 

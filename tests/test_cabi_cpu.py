@@ -29,6 +29,170 @@ def test_version_and_struct_layout(lib):
     assert ctypes.sizeof(_lib.CsGeom) == 2 * 8 + 8 * 8
 
 
+def _header_text():
+    with open(_lib.HEADER_PATH) as fh:
+        return fh.read()
+
+
+def test_derived_argtypes_spot_checks():
+    """The binding is derived from the header: these lists are written out by hand, so a parser that misreads a scalar kind,
+    a char buffer, a struct pointer or a host pointer in the middle of a long list fails here."""
+    from ctypes import POINTER, c_char_p, c_double, c_int32, c_int64, c_size_t, c_void_p
+    P = c_void_p
+    want = {
+        "scint_mean": [P, c_int64, POINTER(c_double), P],
+        "scint_last_error": [c_char_p, c_size_t],
+        "scint_eval_sweep": [P, POINTER(_lib.CsGeom), P, c_int64, P, POINTER(c_int32), POINTER(c_double), c_int64,
+                             c_double, c_int32, c_int64, P, P, P, P, c_size_t, P],
+        "scint_chisq_sweep": [P, POINTER(_lib.CsGeom), P, c_int64, P, POINTER(c_int32), POINTER(c_double), c_int64,
+                              c_double, c_int32, c_int64, P, POINTER(c_int32), P, c_int64, c_int64, P, c_double, P, P, P, c_int64,
+                              P, P, P, c_size_t, P],
+        "scint_sv_sweep_multi": [P, c_int64, c_int64, POINTER(c_int32), POINTER(_lib.ThinGeom), P, c_int64, P, c_int64,
+                                 POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double), c_int64,
+                                 c_double, c_int32, c_int64, P, P, P, P, c_size_t, P],
+    }
+    for name, argtypes in want.items():
+        assert _lib._SIGNATURES[name] == (argtypes, c_int32), name
+    # the pointee type of a device pointer is kept for the checks of _lib.call
+    assert [p.pointee for p in _lib._PARAMS["scint_gerchberg_saxton"] if p.kind == "device"] == \
+        ["scint_c128", "double", "uint8_t", "void", "void"]
+    assert [(p.name, p.const) for p in _lib._PARAMS["scint_mean"] if p.kind != "scalar"] == \
+        [("x", True), ("mean_out", False), ("stream", False)]
+
+
+def test_parser_rejects_what_it_cannot_read():
+    text = _header_text()
+    version, protos = _lib.parse_header(text)
+    assert version == _lib.ABI_VERSION and len(protos) == len(_lib.header_symbols()) == len(_lib._SIGNATURES)
+    anchor = "int32_t scint_device_count(void);"
+    assert anchor in text
+    # an unknown parameter type: the error names the prototype
+    with pytest.raises(ValueError, match=r"unknown type `uint16_t`.*scint_new_thing"):
+        _lib.parse_header(text.replace(anchor, anchor + "\nint32_t scint_new_thing(const double* x, uint16_t flags, void* stream);"))
+    with pytest.raises(ValueError, match=r"unknown device pointee `__half`.*scint_new_thing"):
+        _lib.parse_header(text.replace(anchor, anchor + "\nint32_t scint_new_thing(const __half* x, void* stream);"))
+    # a prototype the strict pattern cannot read (a function-pointer parameter) is an error, not 87 of 88 bound
+    with pytest.raises(ValueError, match=r"cannot read the prototype of scint_new_thing"):
+        _lib.parse_header(text.replace(anchor, anchor + "\nint32_t scint_new_thing(void (*callback)(int32_t), void* stream);"))
+    with pytest.raises(ValueError, match=r"cannot read the prototype of scint_new_thing"):
+        _lib.parse_header(text.replace(anchor, anchor + "\nint64_t scint_new_thing(void* stream);"))
+    with pytest.raises(ValueError, match="SCINT_ABI_VERSION"):
+        _lib.parse_header(text.replace("#define SCINT_ABI_VERSION", "#define SCINT_ABI_VERSIONX"))
+
+
+def test_version_comes_from_the_header(lib):
+    import re
+    m = re.search(r"^#define SCINT_ABI_VERSION (\d+)$", _header_text(), flags=re.M)
+    assert m and _lib.ABI_VERSION == int(m.group(1)) == lib.scint_version() == _lib.call("scint_version")
+
+
+def test_struct_mirrors_are_checked_against_the_header():
+    text = _header_text()
+    for field, struct in (("double fd1_step;", "scint_cs_geom"), ("double fd1, dfd;", "scint_thin_geom")):
+        assert text.count(field) == 1
+        with pytest.raises(ValueError, match=struct):
+            _lib.parse_header(text.replace(field, field + " double extra;"))
+    with pytest.raises(ValueError, match="scint_cs_geom"):       # same count and size, another order
+        _lib.parse_header(text.replace("double tau0, dtau;", "double dtau, tau0;"))
+
+
+def test_call_rejects_wrong_arguments_before_the_library_is_entered(lib):
+    """Every call below would come back with SCINT_E_ARG (a ScintHipError) if the library were entered: M = 0, a negative
+    count, a 0 x 0 transform.  A TypeError naming function and parameter shows that the check came first."""
+    import torch
+    f64 = np.zeros(4)
+
+    def keep(th=None, etas=f64):
+        _lib.call("scint_sweep_keep", th, 0, etas, 4, 1.0, 1.0, None, None, None)
+
+    def fft2(x):
+        _lib.call("scint_fft2", x, None, 0, 0, None, 0, None)
+
+    with pytest.raises(_lib.ScintHipError):                     # the reference case: correct types, the library's own check
+        keep()
+    with pytest.raises(TypeError, match=r"scint_sweep_keep: parameter `etas`.*float32"):
+        keep(etas=np.zeros(4, np.float32))
+    with pytest.raises(TypeError, match=r"scint_sweep_keep: parameter `etas`.*non-contiguous"):
+        keep(etas=np.zeros(8)[::2])
+    with pytest.raises(TypeError, match=r"scint_sweep_keep: parameter `etas`.*Tensor"):
+        keep(etas=torch.zeros(4, dtype=torch.float64))           # a tensor is never host memory
+    with pytest.raises(TypeError, match=r"scint_sweep_keep: parameter `th_cents`.*ndarray"):
+        keep(th=f64)                                             # an array is never device memory
+    ro = np.zeros(8)
+    ro.flags.writeable = False
+    with pytest.raises(_lib.ScintHipError):
+        _lib.call("scint_profile_end", np.zeros(8), None, None, -1)
+    with pytest.raises(TypeError, match=r"scint_profile_end: parameter `ms_out`.*read-only"):
+        _lib.call("scint_profile_end", ro, None, None, -1)
+    with pytest.raises(_lib.ScintHipError):
+        fft2(torch.zeros(4, dtype=torch.complex128))
+    with pytest.raises(TypeError, match=r"scint_fft2: parameter `in`.*complex64"):
+        fft2(torch.zeros(4, dtype=torch.complex64))
+    with pytest.raises(TypeError, match=r"scint_fft2: parameter `in`.*non-contiguous"):
+        fft2(torch.zeros((4, 4), dtype=torch.complex128).t())
+    with pytest.raises(TypeError, match=r"scint_fft2: parameter `in`.*int"):
+        fft2(4096)                                               # a bare address only for void*
+    with pytest.raises(TypeError):                               # a float for a size is not truncated
+        _lib.call("scint_fft2", None, None, 8.0, 16, None, 0, None)
+    with pytest.raises(TypeError, match=r"scint_fft2 takes 7 arguments"):
+        _lib.call("scint_fft2", None, None)
+
+
+def test_a_library_that_lacks_a_declared_symbol(lib, monkeypatch):
+    """`bind` answers a missing symbol with ctypes' own AttributeError -- NOT a RuntimeError, which the emulator fixtures
+    read as "no compiler here" and skip on -- and `load` turns it into the product's rebuild advice."""
+    class Stale:
+        _name = "libstale.so"
+        scint_version = None                                     # every other entry point is missing
+    with pytest.raises(AttributeError, match=r"libstale.so lacks scint_last_error") as err:
+        _lib.bind(Stale())
+    assert not isinstance(err.value, RuntimeError)
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib.ctypes, "CDLL", lambda path: Stale())
+    with pytest.raises(_lib.ScintHipError, match=r"lacks scint_last_error.*rebuild it"):
+        _lib.load()
+
+
+def test_call_passes_correct_arguments(lib):
+    import torch
+    assert _lib.call("scint_version") == _lib.ABI_VERSION
+    n = ctypes.c_size_t()
+    assert _lib.call("scint_sspec_workspace_bytes", 64, 32, n) is None and n.value > 0
+    got = np.zeros(1, dtype=np.uint64)                           # a host array of the pointee's dtype is written in place
+    _lib.call("scint_sspec_workspace_bytes", 64, 32, got)
+    assert got[0] == n.value
+    # None passes for host and device pointers alike, a bare address for void*, a read-only array for a const host pointer:
+    # the library is entered and ITS argument check answers, with its message
+    ro = np.zeros(4)
+    ro.flags.writeable = False
+    with pytest.raises(_lib.ScintHipError, match=r"scint_sweep_keep failed \(status 1\)"):
+        _lib.call("scint_sweep_keep", None, 0, ro, 4, 1.0, 1.0, None, None, 0)
+    with pytest.raises(_lib.ScintHipError, match="null") as err:
+        _lib.call("scint_fft2", None, torch.zeros(4, dtype=torch.complex128), 8, 16, None, 0, None)
+    assert err.value.status == _lib.SCINT_E_ARG
+    with pytest.raises(_lib.ScintHipError, match="bad shape"):
+        _lib.call("scint_sspec_workspace_bytes", 0, 10, n)
+
+
+def test_workspace_for_under_the_emulator(monkeypatch):
+    import os
+    import subprocess
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu"))
+    import emulated
+    try:
+        emu_lib = emulated.install(monkeypatch)
+    except (RuntimeError, OSError, subprocess.CalledProcessError) as exc:    # no usable clang++ on this machine
+        pytest.skip(f"host interpreter could not be built: {exc}")
+    from scintools_amd import device
+    n = ctypes.c_size_t()
+    assert emu_lib.scint_sspec_workspace_bytes(64, 32, ctypes.byref(n)) == 0
+    ws = device.workspace_for("scint_sspec", 64, 32)             # resolves device.workspace (the emulator's) at call time
+    assert ws is device.workspace.get(0) and ws.device.type == "cpu" and ws.numel() >= n.value
+    with pytest.raises(_lib.ScintHipError, match="bad shape"):
+        device.workspace_for("scint_sspec", 0, 10)
+
+
 def test_workspace_queries_and_argument_errors(lib):
     n = ctypes.c_size_t()
     assert lib.scint_sspec_workspace_bytes(4096, 4096, ctypes.byref(n)) == 0
