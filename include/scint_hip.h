@@ -449,6 +449,37 @@ int32_t scint_acf_workspace_bytes(int64_t nf, int64_t nt, size_t* SCINT_HOST byt
 int32_t scint_acf(const double* dyn, int64_t nf, int64_t nt, int32_t subtract_mean, int32_t normalise,
                   double* acf_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Dynspec.calc_acf(method='sspec') (dynspec.py:3798-3807) from the full-frame (halve = 0, prewhite = 0) secondary spectrum in dB
+ * sec_db[R][C] of scint_sspec: acf_out[R][C] = real(fftshift(fft2(10**(fftshift(sec_db) / 10)))), / max if normalise.  R >= 2 and
+ * C >= 16 are powers of two (every full-frame spectrum's are).  -inf dB (an exact zero of power) counts as 0.  Asynchronous. */
+int32_t scint_acf_sspec_workspace_bytes(int64_t R, int64_t C, size_t* SCINT_HOST bytes);
+int32_t scint_acf_sspec(const double* sec_db, int64_t R, int64_t C, int32_t normalise, double* acf_out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- what the no-fit scintillation measurements read from the device (csrc/scintpar.hpp) ---------------------------------
+ * Dynspec.get_scint_params(method='nofit') (dynspec.py:2570-2648), get_acf_tilt (:2358-2413) and cut_dyn (:3158-3271): the ACF
+ * stays in device memory and the reference's host arithmetic gets the few samples it reads.  All asynchronous on `stream`;
+ * no atomics: equal inputs give equal bits.
+ * scint_acf_cuts: cuts_out[0 .. R - R/2) = acf[R/2 + i][C/2] and cuts_out[R - R/2 .. R - R/2 + C - C/2) = acf[R/2][C/2 + j]
+ *   (the integer halves of dynspec.py:2576-2578) for acf[R][C]: a gather, the bits of the ACF's own elements.
+ * scint_dyn_moments: stats_out[3] = (count, mean, population variance) of the pixels of dyn[n] that are finite and non-zero
+ *   (dynspec.py:2633-2635).  Two-stage sums in a fixed order; the variance is a second pass about the mean.  An empty selection
+ *   gives count 0 and NaN, as NumPy.  Workspace: scint_dyn_moments_workspace_bytes().
+ * scint_acf_row_peaks: for k < nrows, col_out[k] = the FIRST column at which acf[rows[k], :] has its maximum (np.argmax; a tie
+ *   resolves to the lowest column, NaN samples are never the maximum), win_out[k][7] = acf[rows[k], col - 3 : col + 4],
+ *   flag_out[k] = 0; a window that would cross column 0 or C is not read: flag_out[k] = 1 and win_out[k] = 0; a rows[k] outside
+ *   [0, R) gives flag_out[k] = 2.  rows, col_out, flag_out: device int32.  1 <= nrows < 2^31, C < 2^31.
+ * scint_segment_cut: segs_out[ii * ntseg + jj][r][c] = dyn[ii * fnum + r][jj * tnum + c] for dyn[nf][nt], ii < nfseg,
+ *   jj < ntseg (dynspec.py:3201-3203); nfseg * fnum <= nf and ntseg * tnum <= nt (SCINT_E_ARG otherwise). */
+int32_t scint_acf_cuts(const double* acf, int64_t R, int64_t C, double* cuts_out, void* stream);
+int32_t scint_dyn_moments_workspace_bytes(size_t* SCINT_HOST bytes);
+int32_t scint_dyn_moments(const double* dyn, int64_t n, double* stats_out, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int32_t scint_acf_row_peaks(const double* acf, int64_t R, int64_t C, const int32_t* rows, int64_t nrows,
+                            int32_t* col_out, double* win_out, int32_t* flag_out, void* stream);
+int32_t scint_segment_cut(const double* dyn, int64_t nf, int64_t nt, int64_t fnum, int64_t tnum, int64_t nfseg,
+                          int64_t ntseg, double* segs_out, void* stream);
+
 /* ---- chi^2: sum((model[:nf,:nt]-dspec)[mask]**2)/N (ththmod.py:364-367) --- */
 /* mask: uint8[nf*nt] or NULL (= isfinite(dspec)).  out: DEVICE double[1].  Asynchronous. */
 int32_t scint_chisq(const double* model, int64_t ld_model, const double* dspec,

@@ -312,7 +312,7 @@ __device__ inline int shift_half(int i, int n) {
 }
 
 enum SrcMode { SRC_ARRAY = 0, SRC_SSPEC = 1, SRC_CS = 2, SRC_MODEL = 3, SRC_MULCONJ = 4, SRC_CONJ = 5,
-               SRC_ACF_IN = 6, SRC_POWER = 7, SRC_CPAD = 8 };
+               SRC_ACF_IN = 6, SRC_POWER = 7, SRC_CPAD = 8, SRC_DBPOWER = 9 };
 
 // Element (row, j) of the row-FFT input, j in [0, fft length).
 struct RowSource {
@@ -327,6 +327,7 @@ struct RowSource {
     // SRC_CPAD: np.pad(x, right, 0) of a COMPLEX x[., wv.nt] = a (a visibility, ththmod.py:1313-1321): reuses a / wv.nt
     double pad;
     // SRC_MODEL: conj(ifftshift(recov)) -- real(ifft2(x)) == real(fft2(conj x))/(R C)
+    // SRC_DBPOWER: 10**(fftshift(sec)/10) of a REAL full-frame spectrum in dB sec[R][C] = wv.dyn (dynspec.py:3802-3803)
     int R, C;
 
     __device__ inline double sspec_d(int r, int c) const { return wv.at(r, c) - m2[0]; }
@@ -348,6 +349,9 @@ struct RowSource {
                 v = mk(x.x * x.x + x.y * x.y, 0.0);
                 break;
             }
+            case SRC_DBPOWER:  // -inf dB (an exact zero of power) gives pow(10, -inf) = 0
+                v = mk(pow(10.0, wv.dyn[(int64_t)shift_half(r, R) * C + shift_half(j, C)] / 10.0), 0.0);
+                break;
             case SRC_SSPEC:
                 if (j >= nt_eff) v = mk(0.0, 0.0);
                 else if (!prewhite) v = mk(sspec_d(r, j), 0.0);
@@ -1306,6 +1310,42 @@ extern "C" int32_t scint_acf(const double* dyn, int64_t nf, int64_t nt, int32_t 
     SCINT_LAUNCH_CHECK();
     return SCINT_OK;
 }
+
+// ------------------------------------------------------------------------------
+// scint_acf_sspec: Dynspec.calc_acf(method='sspec') (dynspec.py:3798-3807)
+// ------------------------------------------------------------------------------
+extern "C" int32_t scint_acf_sspec_workspace_bytes(int64_t R, int64_t C, size_t* bytes) {
+    SCINT_REQUIRE(bytes && R >= 2 && C >= 16 && is_pow2(R) && is_pow2(C), "acf_sspec_workspace_bytes: bad shape");
+    *bytes = fft2_general_ws(R, C, R) + sizeof(double) * (kRedBlocks + 8) + 1024;
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_acf_sspec(const double* sec_db, int64_t R, int64_t C, int32_t normalise, double* acf_out,
+                                   void* workspace, size_t workspace_bytes, void* stream_) {
+    SCINT_REQUIRE(sec_db && acf_out && workspace, "acf_sspec: null pointer");
+    // (a full-frame secondary spectrum: both lengths are powers of two, so fftshift is its own inverse)
+    SCINT_REQUIRE(R >= 2 && C >= 16 && is_pow2(R) && is_pow2(C), "acf_sspec: the spectrum's lengths must be powers of two");
+    size_t need = 0;
+    scint_acf_sspec_workspace_bytes(R, C, &need);
+    if (workspace_bytes < need) { set_error("scint: acf_sspec workspace too small"); return SCINT_E_WORKSPACE; }
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t fft_bytes = align_up(fft2_general_ws(R, C, R), 256);
+    Carver cv((char*)workspace + fft_bytes, workspace_bytes - fft_bytes);
+    double* partial = cv.take<double>(kRedBlocks);
+    RowSource f{};
+    f.mode = SRC_DBPOWER; f.wv.dyn = sec_db; f.R = (int)R; f.C = (int)C;
+    ColSink fs{};
+    fs.mode = SINK_ACF; fs.out_d = acf_out; fs.scale = 1.0;      // real(fftshift(fft2(.)))
+    int32_t rc = fft2_general(f, R, 0.0, R, C, fs, workspace, fft_bytes, stream, /*real_input=*/true);
+    if (rc != SCINT_OK || !normalise) return rc;
+    const int blocks = (int)std::min<int64_t>(kRedBlocks, std::max<int64_t>(1, ceil_div(R * C, 1024)));
+    hipLaunchKernelGGL(max_partial_kernel, dim3(blocks), dim3(256), 0, stream, acf_out, R * C, partial);
+    hipLaunchKernelGGL(scale_by_max_kernel, dim3(blocks), dim3(256), 0, stream, acf_out, R * C, partial, blocks);
+    SCINT_LAUNCH_CHECK();
+    return SCINT_OK;
+}
+
+#include "scintpar.hpp"
 
 // ------------------------------------------------------------------------------
 // scint_chisq_sweep: chisq_calc(modeler(...)) for every curvature in ONE call

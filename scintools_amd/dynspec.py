@@ -21,7 +21,11 @@ reference ``Dynspec``, or plain arrays) with
   3273-3410, 422-440): the cleaning chain; medians, the median filter, gap interpolation and the truncated SVD run on the GPU
   (``scintools_amd/clean.py``).
 
-Velocity / trapezoid rescaling, ``cut_dyn`` and plotting are out of scope.
+* ``calc_acf``, ``get_scint_params(method='nofit')``, ``get_acf_tilt``, ``cut_dyn`` (dynspec.py:3750-3814, 2470-2648,
+  2283-2413, 3158-3271): the ACF stays in HBM; the scintillation scales, the ACF tilt and the segment stacks read what they need
+  from the device (``scintools_amd/scintpar.py``).
+
+Velocity / trapezoid rescaling, the lmfit-driven fits and plotting are out of scope.
 """
 import functools
 import os
@@ -31,7 +35,7 @@ import numpy as np
 import scipy.constants as sc
 import torch
 
-from . import _lib, arcfit, clean, psrflux, units
+from . import _lib, arcfit, clean, psrflux, scintpar, units
 from . import ththmod as thth
 from .device import DeviceBacked, empty, require_gpu, stream_ptr, to_device, workspace_for
 from .device import workspace  # noqa: F401  (kept as a module attribute: the host-interpreter tests swap it per module)
@@ -81,9 +85,10 @@ def _postdark_tables(nrfft, ncfft, device):
             to_device(np.power(np.sin(np.multiply(sc.pi / nrfft, td)), 2), torch.float64))
 
 
-def sspec_device(dyn_t, prewhite=False, halve=True, window="hanning", window_frac=0.1):
+def sspec_device(dyn_t, prewhite=False, halve=True, window="hanning", window_frac=0.1, out=None):
     """Secondary spectrum of a device dynamic spectrum [nf, nt] float64 -> device
-    tensor in dB, shape [(nrfft/2 if halve else nrfft), ncfft] (dynspec.py:3665-3721)."""
+    tensor in dB, shape [(nrfft/2 if halve else nrfft), ncfft] (dynspec.py:3665-3721).
+    ``out``: a contiguous device tensor of that shape to write into (a slice of a stack)."""
     require_gpu()
     nf, nt = (int(v) for v in dyn_t.shape)
     nrfft = int(2 ** (np.ceil(np.log2(nf)) + 1))      # dynspec.py:3677
@@ -93,7 +98,11 @@ def sspec_device(dyn_t, prewhite=False, halve=True, window="hanning", window_fra
     wt, wf = _window_tables(nt, nf, window, window_frac, torch.cuda.current_device())
     pd_fd, pd_td = _postdark_tables(nrfft, ncfft, torch.cuda.current_device()) if prewhite else (None, None)
     ws = workspace_for("scint_sspec", nf, nt)
-    out = empty((nrfft // 2 if halve else nrfft, ncfft), torch.float64)
+    shape = (nrfft // 2 if halve else nrfft, ncfft)
+    if out is None:
+        out = empty(shape, torch.float64)
+    elif tuple(out.shape) != shape:
+        raise ValueError(f"sspec_device: out has shape {tuple(out.shape)}, the spectrum {shape}")
     _lib.call("scint_sspec", dyn_t, nf, nt, wt, wf, 1 if prewhite else 0, 1 if halve else 0, pd_fd, pd_td, out, ws, ws.numel(),
               stream_ptr())
     return out
@@ -103,7 +112,7 @@ class Dynspec:
     """Dynamic-spectrum holder with the reference's attribute names
     (dynspec.py:400-413) and a GPU ``calc_sspec``.
 
-    ``sspec``, ``lamsspec`` and ``lamdyn`` are the reference's NumPy attributes, but a freshly
+    ``sspec``, ``lamsspec``, ``lamdyn`` and ``acf`` are the reference's NumPy attributes, but a freshly
     computed one stays in HBM until it is first read (``device.DeviceBacked``): the chain
     ``scale_dyn -> calc_sspec(lamsteps=True) -> fit_arc`` then never crosses PCIe."""
     sspec = DeviceBacked("sspec")
@@ -111,6 +120,7 @@ class Dynspec:
     chunks = DeviceBacked("chunks")          # the retrieved wavefield chunks (1 GB for a 4096^2 observation): in HBM until read
     wavefield = DeviceBacked("wavefield")
     lamdyn = DeviceBacked("lamdyn")
+    acf = DeviceBacked("acf")                # [2 nf, 2 nt]: 512 MB for a 4096^2 observation; the scales read a few cuts of it
 
     def __init__(self, filename=None, dyn=None, verbose=True, process=False, lamsteps=False,
                  remove_short_subs=True, subint_thresh=2.33, mjd=None):
@@ -259,6 +269,10 @@ class Dynspec:
     correct_dyn = clean.correct_dyn
     auto_processing = clean.auto_processing
 
+    get_scint_params = scintpar.get_scint_params
+    get_acf_tilt = scintpar.get_acf_tilt
+    cut_dyn = scintpar.cut_dyn
+
     @property
     def normsspec(self):
         """2-D normalised secondary spectrum of the last ``norm_sspec`` (masked array); copied
@@ -280,27 +294,28 @@ class Dynspec:
         self._mask_host = value
 
     def calc_acf(self, method='direct', input_dyn=None, normalise=True, window_frac=0.1):
-        """Autocovariance function (dynspec.py:3750-3814), 'direct' method on the GPU:
-        zero-padded fft2 -> |.|^2 -> ifft2 -> fftshift -> real (-> / max).  Sets ``self.acf`` or,
-        with ``input_dyn``, returns it.  Non-finite pixels are not supported here (the reference
-        only excludes them from the mean); method='sspec' is outside the hot path."""
-        if method != 'direct':
-            raise NotImplementedError("calc_acf(method='sspec') is outside the accelerated hot path")
+        """Autocovariance function (dynspec.py:3750-3814) on the GPU.  'direct': zero-padded fft2 -> |.|^2 -> ifft2 ->
+        fftshift -> real (-> / max).  'sspec': the transform of the full-frame secondary spectrum of ``self.dyn`` (the
+        reference takes ``self.dyn`` there even with ``input_dyn``): fftshift -> 10**(./10) -> fft2 -> fftshift -> real
+        (-> / max).  Sets ``self.acf`` -- it stays in HBM until it is first read -- or, with ``input_dyn``, returns a NumPy
+        array.  Non-finite pixels are not supported here (the reference only excludes them from the mean)."""
+        if method not in ('direct', 'sspec'):
+            raise ValueError('Method not understood. Choose "direct" or "sspec"')
         require_gpu()
-        dyn = self.dyn if input_dyn is None else np.asarray(input_dyn)
+        dyn = self.dyn if (input_dyn is None or method == 'sspec') else np.asarray(input_dyn)
         if not np.all(np.isfinite(dyn)):
             raise ValueError("calc_acf on the GPU needs a finite dynamic spectrum (run refill first)")
         dyn_t = to_device(dyn, torch.float64)
-        nf, nt = (int(v) for v in dyn_t.shape)
-        ws = workspace_for("scint_acf", nf, nt)
-        out = empty((2 * nf, 2 * nt), torch.float64)
-        # with input_dyn the reference does NOT subtract the mean (dynspec.py:3786-3789)
-        _lib.call("scint_acf", dyn_t, nf, nt, 1 if input_dyn is None else 0, 1 if normalise else 0, out, ws, ws.numel(), stream_ptr())
-        arr = out.cpu().numpy()
+        if method == 'direct':
+            # with input_dyn the reference does NOT subtract the mean (dynspec.py:3786-3789)
+            out = scintpar.acf_device(dyn_t, subtract_mean=input_dyn is None, normalise=normalise)
+        else:
+            sec_t = sspec_device(dyn_t, prewhite=False, halve=False, window_frac=window_frac)
+            out = scintpar.acf_from_sspec_device(sec_t, normalise=normalise)
         if input_dyn is None:
-            self.acf = arr
+            type(self).acf.park(self, out)       # copied to the host when first read
             return None
-        return arr
+        return out.cpu().numpy()
 
     # ------------------------------------------------------------------ theta-theta
     def prep_thetatheta(self, fw=.1, npad=3, verbose=False, fitting_proc='standard', **kwargs):

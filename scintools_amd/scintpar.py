@@ -1,0 +1,315 @@
+"""Scintillation scales without a fit: ``get_scint_params(method='nofit')``, ``get_acf_tilt`` and ``cut_dyn`` of the reference
+``Dynspec`` (dynspec.py:2470-2648, 2283-2413, 3158-3271), and the device half of ``calc_acf``.
+
+The functions are bound onto ``scintools_amd.dynspec.Dynspec`` as ``arcfit``'s and ``clean``'s are.  What runs where:
+
+* ``calc_acf`` leaves the ``[2 nf, 2 nt]`` ACF in HBM (``Dynspec.acf`` is a ``device.DeviceBacked`` attribute).
+* ``get_scint_params(method='nofit')``: the two half-cuts through the ACF's centre (``scint_acf_cuts``) and count / mean /
+  variance of the valid pixels of ``dyn`` (``scint_dyn_moments``) come from the device; the arithmetic on them is the
+  reference's, statement for statement, on the host.
+* ``get_acf_tilt``: per selected ACF row the first column of the maximum and the 7 samples around it come from the device
+  (``scint_acf_row_peaks``); ``fit_parabola`` per row and the weighted ``np.polyfit`` run on the host.  A row whose 7-sample
+  window would cross the first or last column raises ``ValueError`` (the reference's slice is empty, or short, there).
+* ``cut_dyn``: one upload of ``dyn``; segments cut on the device (``scint_segment_cut``), every segment's secondary spectrum and
+  ACF from device memory, each output stack downloaded once.  ``self.cutacf`` is the one addition: the reference computes every
+  segment's ACF and discards it.
+
+The fitted methods (``acf1d``, ``acf2d_approx``, ``acf2d``, ``sspec``, ``mcmc``) need lmfit and raise ``NotImplementedError``.
+"""
+import numpy as np
+import torch
+
+from . import _lib, device
+from .arcfit import fit_parabola
+
+PEAK_WINDOW = 7            # acf[row, x - 3 : x + 4] (csrc/scintpar.hpp, kPeakWindow)
+
+_NEEDS_LMFIT = ("get_scint_params(method={0!r}) needs lmfit and is outside the accelerated path; "
+                "pass method='nofit' for the scales read off the ACF without a fit")
+
+
+def _lib_ready():
+    _lib.load()
+    device.require_gpu()
+
+
+# ----------------------------------------------------------------------------
+# device calls
+# ----------------------------------------------------------------------------
+def acf_device(dyn_t, subtract_mean=True, normalise=True, out=None):
+    """Direct-method ACF of a device dynamic spectrum [nf, nt] float64 -> device tensor [2 nf, 2 nt] (``scint_acf``)."""
+    _lib_ready()
+    nf, nt = (int(v) for v in dyn_t.shape)
+    ws = device.workspace_for("scint_acf", nf, nt)
+    if out is None:
+        out = device.empty((2 * nf, 2 * nt), torch.float64)
+    _lib.call("scint_acf", dyn_t, nf, nt, 1 if subtract_mean else 0, 1 if normalise else 0, out, ws, ws.numel(),
+              device.stream_ptr())
+    return out
+
+
+def acf_from_sspec_device(sec_t, normalise=True):
+    """``real(fftshift(fft2(10**(fftshift(sec) / 10))))`` (/ max) of a full-frame secondary spectrum in dB on the device."""
+    _lib_ready()
+    R, C = (int(v) for v in sec_t.shape)
+    ws = device.workspace_for("scint_acf_sspec", R, C)
+    out = device.empty((R, C), torch.float64)
+    _lib.call("scint_acf_sspec", sec_t, R, C, 1 if normalise else 0, out, ws, ws.numel(), device.stream_ptr())
+    return out
+
+
+def acf_cuts_device(acf_t):
+    """``(acf[int(nf/2):, int(nt/2)], acf[int(nf/2), int(nt/2):])`` of a device ACF as host arrays: the ACF's own bits."""
+    _lib_ready()
+    R, C = (int(v) for v in acf_t.shape)
+    nfc, ntc = R - R // 2, C - C // 2
+    out = device.empty((nfc + ntc,), torch.float64)
+    _lib.call("scint_acf_cuts", acf_t, R, C, out, device.stream_ptr())
+    cuts = out.cpu().numpy()
+    return cuts[:nfc], cuts[nfc:]
+
+
+def dyn_moments_device(dyn_t):
+    """(count, mean, population variance) of the finite, non-zero pixels of a device array (dynspec.py:2633-2635)."""
+    _lib_ready()
+    stats = device.empty((3,), torch.float64)
+    ws = device.workspace_for("scint_dyn_moments")
+    _lib.call("scint_dyn_moments", dyn_t, int(dyn_t.numel()), stats, ws, ws.numel(), device.stream_ptr())
+    count, mean, var = (float(v) for v in stats.cpu().numpy())
+    return int(count), mean, var
+
+
+def acf_row_peaks_device(acf_t, rows):
+    """Per row of ``rows``: (first column of the row maximum, the 7 samples ``acf[row, x - 3 : x + 4]``, flag) from the device.
+    flag 1: the window would cross the first or last column (its samples are then zero, nothing outside the row is read)."""
+    _lib_ready()
+    R, C = (int(v) for v in acf_t.shape)
+    rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+    if rows.size < 1 or rows.min() < 0 or rows.max() >= R:
+        raise ValueError("acf_row_peaks_device: a row lies outside the ACF")
+    n = int(rows.size)
+    rows_t = device.to_device(rows, torch.int32)
+    cols = device.empty((n,), torch.int32)
+    wins = device.empty((n, PEAK_WINDOW), torch.float64)
+    flags = device.empty((n,), torch.int32)
+    _lib.call("scint_acf_row_peaks", acf_t, R, C, rows_t, n, cols, wins, flags, device.stream_ptr())
+    return cols.cpu().numpy(), wins.cpu().numpy(), flags.cpu().numpy()
+
+
+def segment_cut_device(dyn_t, fnum, tnum, nfseg, ntseg):
+    """The segments ``dyn[ii*fnum:(ii+1)*fnum, jj*tnum:(jj+1)*tnum]`` as one device stack [nfseg * ntseg, fnum, tnum]."""
+    _lib_ready()
+    nf, nt = (int(v) for v in dyn_t.shape)
+    out = device.empty((nfseg * ntseg, fnum, tnum), torch.float64)
+    _lib.call("scint_segment_cut", dyn_t, nf, nt, fnum, tnum, nfseg, ntseg, out, device.stream_ptr())
+    return out
+
+
+# ----------------------------------------------------------------------------
+# Dynspec methods
+# ----------------------------------------------------------------------------
+def get_scint_params(self, method="acf1d", plot=False, alpha=5/3, mcmc=False, full_frame=False, nscale=5, nwalkers=50,
+                     steps=10000, burn=0.25, nitr=1, lnsigma=True, verbose=False, progress=True, display=True,
+                     filename=None, dpi=200, nan_policy='raise', weighted=True, workers=1, tau_vary_2d=True,
+                     tau_input=None, bartlett=True, get_fit_report=True):
+    """Scintillation timescale and bandwidth read off the ACF without a fit (dynspec.py:2470-2648, ``method='nofit'``): the
+    1/e and half-power crossings of the central cuts, the number of scintles and the errors it implies, and the modulation
+    index and bandwidth estimate from the moments of ``dyn``.  Sets ``tau, dnu, amp, wn, dnuerr, tauerr, amperr, wnerr, tscat,
+    nscint, scint_param_method, dnu_est, dnu_esterr, tscat_est, modulation_index``.  The cuts and the moments come from the
+    device, the arithmetic is the reference's.  Every other ``method``, ``mcmc`` and ``plot`` raise ``NotImplementedError``."""
+    if method != 'nofit':
+        raise NotImplementedError(_NEEDS_LMFIT.format(method))
+    if mcmc:
+        raise NotImplementedError("get_scint_params(mcmc=True) needs lmfit and emcee and is outside the accelerated path")
+    if plot:
+        raise NotImplementedError("plotting is outside the accelerated path")
+    cls = type(self)
+    if not cls.acf.present(self):
+        self.calc_acf()
+    ydata_f, ydata_t = acf_cuts_device(cls.acf.tensor(self))
+    count, mean, flux_var = dyn_moments_device(device.to_device(np.asarray(self.dyn, dtype=float), torch.float64))
+
+    xdata_f = self.df * np.linspace(0, len(ydata_f)-1, len(ydata_f))
+    xdata_t = self.dt * np.linspace(0, len(ydata_t)-1, len(ydata_t))
+
+    # Estimate amp and white noise level
+    wn = min([ydata_f[0]-ydata_f[1], ydata_t[0]-ydata_t[1]])
+    amp = max([ydata_f[0] - wn, ydata_t[0] - wn])
+    # Estimate tau. Closest index to 1/e power
+    if np.argwhere(ydata_t < amp/np.e).squeeze().size == 0:
+        tau = self.dt if ydata_t[1] < 0 else self.tobs
+    else:
+        tau = xdata_t[np.argwhere(ydata_t < amp/np.e).squeeze()[0]]
+    # Estimate dnu. Closest index to 1/2 power
+    if np.argwhere(ydata_f < amp/2).squeeze().size == 0:
+        dnu = self.df if ydata_f[1] < 0 else self.bw
+    else:
+        dnu = xdata_f[np.argwhere(ydata_f < amp/2).squeeze()[0]]
+
+    # crop arrays to nscale number of scales, or 5 samples
+    if not full_frame:
+        t_inds = np.argwhere(xdata_t <= nscale*tau).squeeze()
+        f_inds = np.argwhere(xdata_f <= nscale*dnu).squeeze()
+        if nscale*tau <= 5*self.dt:
+            t_inds = np.argwhere(xdata_t <= 5*self.dt).squeeze()
+        if nscale*dnu <= 5*self.df:
+            f_inds = np.argwhere(xdata_f <= 5*self.df).squeeze()
+        xdata_t = xdata_t[t_inds]
+        ydata_t = ydata_t[t_inds]
+        xdata_f = xdata_f[f_inds]
+        ydata_f = ydata_f[f_inds]
+
+    self.tau = tau
+    self.dnu = dnu
+    self.amp = amp
+    self.wn = wn
+
+    # Estimated number of scintles
+    tau_half = xdata_t[np.argmin(abs(ydata_t - amp/2))]  # half power
+    if tau_half < self.dt:
+        tau_half = self.dt
+    elif tau_half > self.tobs:
+        tau_half = self.tobs
+    nscint = (1 + 0.2*self.bw/(self.dnu)) * \
+        (1 + 0.2*self.tobs/(tau_half))
+    # Estimated errors
+    self.dnuerr = dnu / np.sqrt(nscint)
+    self.tauerr = tau / np.sqrt(nscint)
+    self.amperr = amp / np.sqrt(nscint)
+    self.wnerr = wn / np.sqrt(nscint)
+    self.tscat = 1/(2*np.pi*self.dnu)  # scattering timescale
+    self.nscint = nscint
+    self.scint_param_method = 'nofit'
+
+    flux_var_est = mean**2
+    # Estimate of scint bandwidth
+    self.dnu_est = self.df * (flux_var/flux_var_est - 1)
+    if self.dnu_est < 0:
+        self.dnu_est = 0
+    self.dnu_esterr = self.dnu_est / np.sqrt(nscint)
+    if self.dnu_est > 0:
+        self.tscat_est = 1/(2*np.pi*self.dnu_est)  # scattering timescale
+    else:
+        self.tscat_est = 0
+    self.modulation_index = np.sqrt(flux_var)/mean
+    return
+
+
+def get_acf_tilt(self, plot=False, tmax=None, fmax=None, display=True, filename=None, nscale=0.8, nscaleplot=2, nmin=5,
+                 dpi=200, method='acf1d', tmaxplot=None, fmaxplot=None):
+    """Tilt of the ACF, proportional to the phase gradient parallel to Veff (dynspec.py:2283-2413): the peak of every
+    frequency-lag row within ``fmax`` (default ``nscale * dnu``; at least ``nmin`` rows) from a 7-point parabola, then a weighted
+    straight line through the peaks.  Sets ``acf_tilt`` (min/MHz), ``acf_tilt_err`` and ``fse_tilt``.  Row maxima and windows
+    come from the device, the fits run on the host.  Without ``dnu`` it calls ``get_scint_params(method=method)``: only
+    ``method='nofit'`` is available here.  A peak closer than 3 columns to an edge raises ``ValueError``."""
+    if plot:
+        raise NotImplementedError("plotting is outside the accelerated path")
+    cls = type(self)
+    if not cls.acf.present(self):
+        self.calc_acf()
+    if not hasattr(self, 'dnu'):
+        self.get_scint_params(method=method)
+
+    if tmax is None:
+        tmax = nscale*self.tau/60
+    if fmax is None:
+        fmax = nscale*self.dnu
+
+    nr, nc = cls.acf.shape(self)
+    t_delays = np.linspace(-self.tobs/60, self.tobs/60, nc+1)[:-1]
+    f_shifts = np.linspace(-self.bw, self.bw, nr+1)[:-1]
+
+    inds = np.argwhere(abs(f_shifts) <= fmax)
+    if len(inds) < nmin:
+        inds = np.argwhere(abs(f_shifts) <= nmin*self.df)
+    if len(inds) < 1:
+        raise ValueError("get_acf_tilt: no frequency lag within fmax")
+    cols, wins, flags = acf_row_peaks_device(cls.acf.tensor(self), inds[:, 0])
+    if np.any(flags != 0):
+        bad = int(inds[np.flatnonzero(flags)[0], 0])
+        raise ValueError(f"get_acf_tilt: the maximum of ACF row {bad} lies within 3 columns of the edge: "
+                         "no 7-sample window for the parabola fit")
+    peak_array = []
+    peakerr_array = []
+    y_array = []
+
+    # Fit parabolas to find the peak in each frequency-slice
+    for k, ii in enumerate(inds):
+        x_max = int(cols[k])
+        ydata = wins[k]
+        xdata = t_delays[x_max - 3:x_max + 4]
+        yfit, peak, peakerr = fit_parabola(xdata, ydata)
+        peak_array.append(peak)
+        peakerr_array.append(peakerr)
+        y_array.append(f_shifts[ii])
+    peak_array = np.array(peak_array).squeeze()
+    y_array = np.array(y_array).squeeze()
+    peakerr_array = np.array(peakerr_array).squeeze()
+
+    # Now do a weighted fit of a straight line to the peaks
+    params, pcov = np.polyfit(peak_array, y_array, 1, cov=True, w=1/peakerr_array)
+    xfit = (y_array - params[1])/params[0]
+
+    # Get parameter errors
+    errors = []
+    for i in range(len(params)):  # for each parameter
+        errors.append(np.absolute(pcov[i][i])**0.5)
+    errors = np.array(errors).squeeze()
+    res = np.array(peak_array - xfit).squeeze()
+    reduced_chi_sq = np.sum(res**2/peakerr_array**2)/(len(xfit) - 2)
+    errors *= np.sqrt(reduced_chi_sq)
+
+    self.acf_tilt = 1/(float(params[0].squeeze()))  # make min/MHz
+    acf_tilt_err = float(errors[0].squeeze()) * \
+        1/float(params[0].squeeze())**2
+
+    # Compute finite scintle error
+    N = (1 + 0.2*self.bw/(self.dnu)) * \
+        (1 + 0.2*self.tobs/(self.tau*np.log(2)))  # 2*half power
+    fse_tau = self.tau/(2*np.sqrt(N))
+    fse_dnu = self.dnu/(2*np.sqrt(N))
+
+    fse_tilt = self.acf_tilt * np.sqrt((fse_dnu/self.dnu)**2 +
+                                       (fse_tau/self.tau)**2)
+
+    self.fse_tilt = fse_tilt
+    self.acf_tilt_err = acf_tilt_err
+    return
+
+
+def cut_dyn(self, tcuts=0, fcuts=0, plot=False, filename=None, dpi=200, lamsteps=False, maxfdop=np.inf, figsize=(8, 13),
+            display=True):
+    """Cut the dynamic spectrum into ``tcuts + 1`` segments in time and ``fcuts + 1`` in frequency (dynspec.py:3158-3271) and
+    take every segment's secondary spectrum and ACF.  Sets ``cutdyn [fcuts+1, tcuts+1, fnum, tnum]`` and ``cutsspec [.., nrfft,
+    ncfft]`` as the reference does (floor division, remainders dropped; ``lamsteps`` only changes the y-axis of a segment's
+    spectrum in the reference, not its data, so it changes nothing here) and -- the one addition -- ``cutacf [.., 2 fnum,
+    2 tnum]``, which the reference computes and discards.  ``dyn`` is uploaded once, the segments never visit the host, each
+    stack is downloaded once."""
+    if plot:
+        raise NotImplementedError("plotting is outside the accelerated path")
+    from .dynspec import sspec_device
+    _lib_ready()
+    nchan = len(self.freqs)  # re-define in case of trimming
+    nsub = len(self.times)
+    fnum = int(np.floor(nchan/(fcuts + 1)))
+    tnum = int(np.floor(nsub/(tcuts + 1)))
+    if fcuts < 0 or tcuts < 0 or fnum < 2 or tnum < 5:
+        raise ValueError(f"cut_dyn: segments of {fnum} channels x {tnum} sub-integrations are too small (at least 2 x 5)")
+    dyn = np.asarray(self.dyn, dtype=float)
+    if dyn.shape[0] < (fcuts + 1) * fnum or dyn.shape[1] < (tcuts + 1) * tnum:
+        raise ValueError("cut_dyn: dyn is smaller than its frequency and time axes")
+    if not np.all(np.isfinite(dyn[:(fcuts + 1) * fnum, :(tcuts + 1) * tnum])):
+        raise ValueError("cut_dyn on the GPU needs a finite dynamic spectrum (run refill first)")
+    # find the right fft lengths for rows and columns
+    nrfft = int(2**(np.ceil(np.log2(int(fnum)))+1)/2)
+    ncfft = int(2**(np.ceil(np.log2(int(tnum)))+1))
+    nseg = (fcuts + 1) * (tcuts + 1)
+    segs = segment_cut_device(device.to_device(dyn, torch.float64), fnum, tnum, fcuts + 1, tcuts + 1)
+    sspecs = device.empty((nseg, nrfft, ncfft), torch.float64)
+    acfs = device.empty((nseg, 2 * fnum, 2 * tnum), torch.float64)
+    for k in range(nseg):
+        sspec_device(segs[k], out=sspecs[k])
+        acf_device(segs[k], subtract_mean=False, out=acfs[k])     # (with input_dyn the reference subtracts no mean)
+    self.cutdyn = segs.cpu().numpy().reshape(fcuts + 1, tcuts + 1, fnum, tnum)
+    self.cutsspec = sspecs.cpu().numpy().reshape(fcuts + 1, tcuts + 1, nrfft, ncfft)
+    self.cutacf = acfs.cpu().numpy().reshape(fcuts + 1, tcuts + 1, 2 * fnum, 2 * tnum)
