@@ -774,6 +774,39 @@ int32_t scint_slow_ft_workspace_bytes(int64_t nt, int64_t nf, size_t* SCINT_HOST
 int32_t scint_slow_ft(const double* dyn /*[nt][nf]*/, int64_t nt, int64_t nf, const double* fscale /*[nf] device*/,
                       scint_c128* out /*[nt][nf]*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The velocity and trapezoid rescalings of Dynspec.scale_dyn (dynspec.py:3961-4128); kernels in csrc/scale.hpp, DESIGN.md 4n.
+ *
+ * scint_spline_resample_rows: every ROW of dyn[nf, nt] is interpolated with the not-a-knot cubic spline (scipy
+ *   interp1d(kind='cubic')) from the knots x[nt] (ascending, any spacing, shared by all rows) to nout targets: out[nf, nout],
+ *   out[r, j] = S_r(target j), not flipped.  The mathematics and the arguments are scint_spline_resample's, with the time axis in
+ *   the place of the frequency axis: h[nt-1], sub/inv/sup[nt] the Thomas factors (DEVICE), end[4] the not-a-knot ends (HOST),
+ *   idx[nout] the interval of every target and coef[nout][4] its weights; idx must be NON-DECREASING (targets ascending), because
+ *   a block of knots evaluates the contiguous range of targets that falls into it.
+ *   A workgroup takes up to 64 rows and one block of `block` interior knots, started `warm` knots early from zero on either side
+ *   (block <= 0 or >= nt-2: one block, the plain sequential sweep of every row; `warm` is then ignored); it stages its tile in
+ *   LDS, solves there and evaluates its targets from LDS, so the moments never reach memory and no workspace is used.  Only when
+ *   ONE block is asked for and min(block + 2 warm + 4, nt) exceeds 7679 knots the rows are swept through a workspace of nf*nt
+ *   doubles (scint_spline_resample_rows_workspace_bytes says which: 256 bytes, which may be NULL, or nf*nt*8).
+ *   A non-finite pixel spreads over what one sweep covers: its whole row with one block, its neighbourhood otherwise (the caller
+ *   tests the mean and asks for one block).  float64, no atomics, equal inputs give equal bits.  Asynchronous on `stream`.
+ *   Limits: 1 <= nf <= 65535, 4 <= nt < 2^31, 1 <= nout < 2^31.
+ *
+ * scint_trap_scale: out[nf, nt] of scale_dyn(scale='trapezoid').  v[f][t] = ((dyn[f][t] - mean) * cw[t]) * sw[f] in that order
+ *   (cw == sw == NULL: v = dyn - mean; `mean` is the caller's np.mean of the host array); row f keeps nkeep[f] samples (DEVICE
+ *   int32, clamped to [0, nt]): out[f][j] = np.interp(np.linspace(times[0], times[nt-1], nkeep[f])[j], times, v[f]) for
+ *   j < nkeep[f] and +0.0 after.  times[nt] ascending, any spacing.  np.linspace and np.interp are reproduced operation by
+ *   operation (step = (stop - start)/(n - 1), j*step + start, the last sample set to stop; the bracket j with times[j] <= x,
+ *   slope*(x - times[j]) + v[j] without contraction and NumPy's NaN retries), so the result equals NumPy's bit for bit.
+ *   Limits: 1 <= nf <= 65535, nt >= 1.  Asynchronous on `stream`. */
+int32_t scint_spline_resample_rows_workspace_bytes(int64_t nf, int64_t nt, int64_t block, int64_t warm, size_t* SCINT_HOST bytes);
+int32_t scint_spline_resample_rows(const double* dyn, int64_t nf, int64_t nt, const double* h, const double* sub,
+                                   const double* inv, const double* sup, const double* SCINT_HOST end /*[4]*/,
+                                   int64_t block, int64_t warm, const int32_t* idx, const double* coef, int64_t nout,
+                                   double* out, void* workspace, size_t workspace_bytes, void* stream);
+int32_t scint_trap_scale(const double* dyn, int64_t nf, int64_t nt, double mean, const double* cw, const double* sw,
+                         const double* times, const int32_t* nkeep, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,8 @@
 """Arc normalisation of the secondary spectrum on the GPU: the numerics of
 
 * ``Dynspec.scale_dyn(scale='lambda')``  dynspec.py:3928-3959  -> ``scint_spline_resample``
+* ``Dynspec.scale_dyn(scale='velocity')``  dynspec.py:3961-4079  -> ``scint_spline_resample_rows``
+* ``Dynspec.scale_dyn(scale='trapezoid')`` dynspec.py:4081-4128  -> ``scint_trap_scale``
 * ``Dynspec.norm_sspec``                 dynspec.py:1920-2183  -> ``scint_norm_sspec`` +
                                                                    ``scint_masked_colavg`` (+ ``scint_row_nanmean``)
 * ``Dynspec.fit_arc``                    dynspec.py:970-1313   -> ``scint_block_std`` + norm_sspec
@@ -8,7 +10,7 @@
 The O(rows x columns) work (cubic-spline resample of every time column, the per-delay-row
 ``np.interp`` resample, masked means) runs in HIP kernels; the 1-D profile logic of ``fit_arc``
 (Savitzky-Golay smoothing, peak walk, parabola fit) stays on the host exactly as in the
-reference.  Plotting, ``velocity`` scaling, ``interp_nan`` (scipy griddata) and
+reference.  Plotting, ``norm_sspec(velocity=True)`` / ``fit_arc(velocity=True)``, ``interp_nan`` (scipy griddata) and
 ``fit_spectrum`` (lmfit) are outside the accelerated path and raise ``NotImplementedError``.
 """
 import ctypes
@@ -182,6 +184,245 @@ def scale_dyn_lambda(self, spacing="auto"):
 
 
 # ----------------------------------------------------------------------------
+# scale_dyn(scale='velocity' | 'orbit')
+# ----------------------------------------------------------------------------
+_ROWS_LDS = 7680           # doubles of LDS one workgroup of the row kernel holds (csrc/scale.hpp, kRowsLds)
+_ROWS_TRANSPOSE_MIN = 1 << 24     # pixels from which the blocked row resample goes through a transpose and the column kernel
+
+
+def spline_rows_route(x):
+    """How ``spline_resample_rows_device`` will sweep the ascending knots x: ('blocked', block, warm) when the time axis is cut
+    into warm-started blocks, ('lds', 0, 0) for one sequential sweep per row inside LDS, ('workspace', 0, 0) for one sequential
+    sweep per row through HBM (an axis that cannot be blocked and does not fit the tile).  A host-side decision from the
+    Thomas factors alone (``_spline_blocks``); non-finite data turn 'blocked' into one of the other two at run time."""
+    x = np.asarray(x, dtype=float)
+    h, sub, inv, sup, end = _spline_system(x)
+    block, warm = _spline_blocks(sub, inv, sup, len(x))
+    if block:
+        return "blocked", block, warm
+    return ("lds" if len(x) + 1 <= _ROWS_LDS else "workspace"), 0, 0
+
+
+def spline_resample_rows_device(dyn_t, x, xnew, force_one_block=False):
+    """Cubic-spline (scipy ``interp1d(kind='cubic')``) resample of every ROW of the device array dyn_t[nf, nt] from the knots
+    `x` (length nt) to `xnew` (dynspec.py:4062-4074): out[nf, len(xnew)] on the device.  `x` in any order without duplicates
+    (interp1d sorts), `xnew` in any order inside the range of `x`.  ``force_one_block``: never block the time axis (the tests
+    compare the two)."""
+    require_gpu()
+    x = np.asarray(x, dtype=float)
+    nf, nt = (int(v) for v in dyn_t.shape)
+    if nt != len(x):
+        raise ValueError("x and y arrays must be equal in length along interpolation axis.")
+    if nt < 4:
+        raise ValueError("The number of derivatives at boundaries does not match: expected 1, got 0+0")
+    d = np.diff(x)
+    if not np.all(d > 0):                   # interp1d sorts an unsorted axis
+        order = np.argsort(x, kind="mergesort")
+        x = x[order]
+        if np.any(np.diff(x) <= 0):
+            raise ValueError("Expect x to not have duplicates")
+        dyn_t = dyn_t[:, to_device(order.astype(np.int64), torch.int64)].contiguous()
+    xnew = np.asarray(xnew, dtype=float)
+    if xnew.ndim != 1 or len(xnew) < 1:
+        raise ValueError("spline_resample_rows_device: xnew must be one-dimensional and not empty")
+    if xnew.min() < x[0] or xnew.max() > x[-1]:
+        raise ValueError("A value in x_new is outside the interpolation range.")
+    unsort = None
+    if np.any(np.diff(xnew) < 0):           # the kernel wants ascending targets: evaluate sorted, hand back in the caller's order
+        order = np.argsort(xnew, kind="mergesort")
+        unsort = np.empty_like(order)
+        unsort[order] = np.arange(len(order))
+        xnew = xnew[order]
+    h, sub, inv, sup, end = _spline_system(x)
+    idx = np.clip(np.searchsorted(x, xnew, side="right") - 1, 0, nt - 2)
+    hk = h[idx]
+    A = (x[idx + 1] - xnew) / hk
+    B = (xnew - x[idx]) / hk
+    coef = np.stack([A, B, (A**3 - A) * hk**2 / 6.0, (B**3 - B) * hk**2 / 6.0], axis=1)
+    block, warm = (0, 0) if force_one_block else _spline_blocks(sub, inv, sup, nt)
+    if block and nf * nt >= _ROWS_TRANSPOSE_MIN and len(xnew) <= 65535:
+        # Measured at 4096 x 4096 (profiles/scale_timing.json): transpose, the column kernel and transpose back take 2.15 ms,
+        # the row kernel 2.34 ms, with equal bits; at 1024 x 1024 the row kernel wins (0.73 against 0.80 ms).  The column kernel
+        # writes its rows flipped, so it gets the targets reversed.
+        out = spline_resample_device(dyn_t.t().contiguous(), x, xnew[::-1]).t().contiguous()
+        return out if unsort is None else out[:, to_device(unsort.astype(np.int64), torch.int64)].contiguous()
+    if block:
+        # A NaN/inf pixel must poison its whole row, as scipy's sequential solve does; warm-started blocks would confine it.
+        # One device reduction tells: the mean is non-finite iff some pixel is.
+        m = ctypes.c_double()
+        _lib.call("scint_mean", dyn_t, nf * nt, m, stream_ptr())
+        if not np.isfinite(m.value):
+            block, warm = 0, 0
+    ws = workspace_for("scint_spline_resample_rows", nf, nt, block, warm)
+    out = empty((nf, len(xnew)), torch.float64)
+    dev = lambda v: to_device(np.ascontiguousarray(v, dtype=float), torch.float64)
+    h_t, sub_t, inv_t, sup_t, coef_t = dev(h), dev(sub), dev(inv), dev(sup), dev(coef)
+    idx_t = to_device(idx.astype(np.int32), torch.int32)
+    _lib.call("scint_spline_resample_rows", dyn_t, nf, nt, h_t, sub_t, inv_t, sup_t, np.ascontiguousarray(end, dtype=float),
+              block, warm, idx_t, coef_t, len(xnew), out, ws, ws.numel(), stream_ptr())
+    if unsort is not None:
+        out = out[:, to_device(unsort.astype(np.int64), torch.int64)].contiguous()
+    return out
+
+
+def velocity_grid(veff):
+    """(vc_orig, vc_new) of dynspec.py:4056-4068: the cumulative effective velocity and its even grid with the reference's two
+    clamps, in the precision of `veff` (the reference's is float128), then both as float64 -- which is what interp1d hands to
+    its spline: make_interp_spline casts the knots, BSpline.__call__ the targets."""
+    vc_orig = np.cumsum(veff)  # original cumulative sum of velocity
+    vc_new = np.linspace(np.min(vc_orig), np.max(vc_orig), len(vc_orig))
+    if max(vc_new) > max(vc_orig):
+        vc_new[np.argmax(vc_new)] = max(vc_orig)
+    if min(vc_new) < min(vc_orig):
+        vc_new[np.argmin(vc_new)] = min(vc_orig)
+    return np.asarray(vc_orig, dtype=np.float64), np.asarray(vc_new, dtype=np.float64)
+
+
+def velocity_resample_device(dyn_t, veff):
+    """Every channel of the device array dyn_t[nf, nt] resampled onto equal steps of the cumulative effective velocity
+    (dynspec.py:4055-4074), for `veff` [nt] from any source (no ephemerides needed): out[nf, nt] on the device."""
+    vc_orig, vc_new = velocity_grid(np.asarray(veff))
+    return spline_resample_rows_device(dyn_t, vc_orig, vc_new)
+
+
+def scale_dyn_velocity(self, pars=None, parfile=None, s=None, d=None, vism_ra=None, vism_dec=None, Omega=None, inc=None,
+                       vism_zeta=None, zeta=None):
+    """dyn(f, t) -> dyn(f, cumulative effective velocity) (dynspec.py:3961-4079).  Sets ``vdyn`` (and ``vlamdyn`` when ``lamdyn``
+    is there), ``veff_ra``, ``veff_dec``.  The argument logic is the reference's, line by line; the ephemeris functions are
+    looked up in ``scint_utils`` when called, as the reference imports them then."""
+    from . import scint_models, scint_utils
+
+    if pars is None and parfile is None:
+        raise ValueError('Requires dictionary of parameters ' +
+                         'or .par file for velocity calculation')
+    if parfile is not None:
+        pars = scint_utils.read_par(parfile)
+    cls = type(self)
+    mjd = np.asarray(self.mjd, dtype=np.longdouble) + \
+        np.asarray(self.times, dtype=np.longdouble) / 86400
+
+    ssb_delays = scint_utils.get_ssb_delay(mjd, pars['RAJ'], pars['DECJ'])
+    mjd += np.divide(ssb_delays, 86400)  # add ssb delay
+    vearth_ra, vearth_dec = scint_utils.get_earth_velocity(mjd, pars['RAJ'], pars['DECJ'])
+    true_anomaly = scint_utils.get_true_anomaly(mjd, pars)
+    if 's' not in pars.keys():
+        if s is None:
+            raise ValueError('Requires screen distance s in ' +
+                             'parameter dictionary, or as input')
+        pars['s'] = s
+    if 'd' not in pars.keys():
+        if d is None:
+            raise ValueError('Requires pulsar distance d in ' +
+                             'parameter dictionary, or as input')
+        pars['d'] = d
+    if 'KIN' not in pars.keys():
+        if inc is None:
+            raise ValueError('Requires inclination angle (KIN) in ' +
+                             'parameter dictionary, or as input inc')
+        pars['KIN'] = inc
+    if 'KOM' not in pars.keys():
+        if Omega is None:
+            raise ValueError('Requires ascending node (KOM) in ' +
+                             'parameter dictionary, or as input Omega')
+        pars['KOM'] = Omega
+
+    veff_ra, veff_dec, vp_ra, vp_dec = scint_models.effective_velocity_annual(pars, true_anomaly, vearth_ra, vearth_dec, mjd=mjd)
+    veff2, veff_ra, veff_dec = effective_velocity_squared(pars, veff_ra, veff_dec, vism_ra=vism_ra, vism_dec=vism_dec,
+                                                          vism_zeta=vism_zeta, zeta=zeta)
+    veff = np.sqrt(veff2)
+    vc_orig, vc_new = velocity_grid(veff)
+    dyn_t = to_device(np.asarray(self.dyn, dtype=float), torch.float64)
+    v_t = spline_resample_rows_device(dyn_t, vc_orig, vc_new)
+    if cls.lamdyn.present(self):
+        vlam_t = spline_resample_rows_device(cls.lamdyn.tensor(self), vc_orig, vc_new)
+    self.veff_ra = veff_ra
+    self.veff_dec = veff_dec
+    cls.vdyn.park(self, v_t)                            # stay in HBM until the host reads them
+    if cls.lamdyn.present(self):
+        cls.vlamdyn.park(self, vlam_t)
+
+
+def effective_velocity_squared(pars, veff_ra, veff_dec, vism_ra=None, vism_dec=None, vism_zeta=None, zeta=None):
+    """veff**2 along the anisotropy, or isotropic, with the ISM velocity removed (dynspec.py:4018-4053).  Returns
+    (veff2, veff_ra, veff_dec); the two components are changed IN PLACE where the reference does so (``-=`` on arrays)."""
+    # anisotropic case
+    if ('zeta' in pars.keys()) or (zeta is not None):
+        if 'zeta' in pars.keys():
+            zeta = pars['zeta']
+        zeta *= np.pi / 180  # make radians
+        # vism in direction of anisotropy
+        if 'vism_zeta' in pars.keys():
+            vism_zeta = pars['vism_zeta']
+            veff2 = (veff_ra * np.sin(zeta) + veff_dec * np.cos(zeta) - vism_zeta)**2
+        elif vism_zeta is not None:
+            veff2 = (veff_ra * np.sin(zeta) + veff_dec * np.cos(zeta) - vism_zeta)**2
+        else:  # no vism_zeta: RA and DEC velocities, if any
+            if 'vism_ra' in pars.keys():
+                veff_ra -= pars['vism_ra']
+            elif vism_ra is not None:
+                veff_ra -= vism_ra
+            if 'vism_dec' in pars.keys():
+                veff_dec -= pars['vism_dec']
+            elif vism_dec is not None:
+                veff_dec -= vism_dec
+            veff2 = (veff_ra * np.sin(zeta) + veff_dec * np.cos(zeta))**2
+    # isotropic case
+    else:
+        if 'vism_ra' in pars.keys():
+            veff_ra -= pars['vism_ra']
+        elif vism_ra is not None:
+            veff_ra -= vism_ra
+        if 'vism_dec' in pars.keys():
+            veff_dec -= pars['vism_dec']
+        elif vism_dec is not None:
+            veff_dec -= vism_dec
+        veff2 = veff_ra**2 + veff_dec**2
+    return veff2, veff_ra, veff_dec
+
+
+# ----------------------------------------------------------------------------
+# scale_dyn(scale='trapezoid')
+# ----------------------------------------------------------------------------
+def trapezoid_keep(freqs, times):
+    """Samples every channel keeps (dynspec.py:4111-4118): ``len(np.argwhere(times <= maxtime))`` for ascending times."""
+    nf = len(freqs)
+    scalefrac = 1 / (max(freqs) / min(freqs))
+    timestep = max(times) * (1 - scalefrac) / (nf + 1)  # time step
+    maxtime = max(times) - (nf - (np.arange(nf) + 1)) * timestep
+    return np.searchsorted(times, maxtime, side="right").astype(np.int32)
+
+
+def trap_scale_device(dyn, freqs, times, window='hanning', window_frac=0.1):
+    """The trapezoid rescale of the HOST array dyn[nf, nt] (dynspec.py:4081-4128) in one device pass: every channel's time axis
+    stretched in proportion to its frequency, zeros after.  Returns the device tensor [nf, nt]."""
+    from .dynspec import get_window
+    dyn = np.asarray(dyn, dtype=float)
+    nf, nt = dyn.shape
+    freqs = np.asarray(freqs, dtype=float)
+    times = np.ascontiguousarray(times, dtype=float)
+    if len(freqs) != nf or len(times) != nt:
+        raise ValueError(f"trap_scale_device: dyn is {nf} x {nt}, freqs has {len(freqs)} and times {len(times)} entries")
+    if np.any(np.diff(times) < 0):
+        raise ValueError("trap_scale_device: times must be ascending")
+    cw_t = sw_t = None
+    if window is not None:
+        cw, sw = get_window(nt, nf, window=window, frac=window_frac)       # ValueError for an unknown window
+    require_gpu()
+    if window is not None:
+        cw_t, sw_t = to_device(cw, torch.float64), to_device(sw, torch.float64)
+    mean = float(np.mean(dyn))
+    out = empty((nf, nt), torch.float64)
+    _lib.call("scint_trap_scale", to_device(dyn, torch.float64), nf, nt, mean, cw_t, sw_t, to_device(times, torch.float64),
+              to_device(trapezoid_keep(freqs, times), torch.int32), out, stream_ptr())
+    return out
+
+
+def scale_dyn_trapezoid(self, window='hanning', window_frac=0.1):
+    """Sets ``trapdyn`` (dynspec.py:4081-4128); it stays in HBM until the host reads it."""
+    type(self).trapdyn.park(self, trap_scale_device(self.dyn, self.freqs, self.times, window=window, window_frac=window_frac))
+
+
+# ----------------------------------------------------------------------------
 # norm_sspec
 # ----------------------------------------------------------------------------
 def _sspec_for(self, lamsteps):
@@ -209,7 +450,7 @@ def norm_sspec(self, eta=None, delmax=None, plot=False, startbin=1, maxnormfac=5
     if plot:
         raise NotImplementedError("plotting is outside the accelerated hot path")
     if velocity:
-        raise NotImplementedError("velocity scaling needs Dynspec.scale_dyn('velocity') (outside the hot path)")
+        raise NotImplementedError("the arc normalisation of the velocity-scaled spectrum (vsspec / vlamsspec) is not ported yet")
     if interp_nan:
         raise NotImplementedError("interp_nan (scipy.interpolate.griddata) is outside the accelerated path")
     if fit_spectrum:
@@ -373,7 +614,7 @@ def fit_arc(self, asymm=False, plot=False, delmax=None, numsteps=1e4, startbin=3
     if plot or plot_spec:
         raise NotImplementedError("plotting is outside the accelerated hot path")
     if velocity:
-        raise NotImplementedError("velocity scaling needs Dynspec.scale_dyn('velocity') (outside the hot path)")
+        raise NotImplementedError("the arc normalisation of the velocity-scaled spectrum (vsspec / vlamsspec) is not ported yet")
     require_gpu()
     if not hasattr(self, "tdel"):
         self.calc_sspec()
@@ -600,8 +841,7 @@ def calc_scattered_image(self, input_sspec=None, input_eta=None, input_fdop=None
     if plot or plot_fit:
         raise NotImplementedError("plotting is outside the accelerated hot path")
     if trap:
-        raise NotImplementedError("velocity / trap need Dynspec.scale_dyn('velocity'/'trapezoid'), "
-                                  "which is outside the accelerated hot path")
+        raise NotImplementedError("the scattered image of the trapezoid-scaled spectrum (trapsspec) is not ported yet")
     cls = type(self)
     if input_sspec is None:
         if lamsteps:

@@ -251,7 +251,7 @@ def correct_dyn(self, svd=True, nmodes=1, frequency=True, time=True, lamsteps=Fa
     the plain case the working array IS ``self.dyn`` until the first divide makes a new one, so the in-place NaN -> 0, 0 -> NaN and
     NaN -> 0 steps on ``self.dyn`` hit it too; with ``lamsteps`` they hit ``self.dyn`` alone, which nothing then reads."""
     if velocity:
-        raise NotImplementedError("velocity scaling is outside the accelerated hot path")
+        raise NotImplementedError("correct_dyn of the velocity-scaled spectrum (vdyn) is not ported yet")
     if svd:
         nmodes = _check_nmodes(nmodes)
     if hasattr(self, 'svd_model'):

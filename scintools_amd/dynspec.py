@@ -25,7 +25,10 @@ reference ``Dynspec``, or plain arrays) with
   2283-2413, 3158-3271): the ACF stays in HBM; the scintillation scales, the ACF tilt and the segment stacks read what they need
   from the device (``scintools_amd/scintpar.py``).
 
-Velocity / trapezoid rescaling, the lmfit-driven fits and plotting are out of scope.
+* ``scale_dyn(scale='velocity' | 'orbit' | 'trapezoid')`` and ``calc_sspec(velocity=True | trap=True)`` (dynspec.py:3961-4128):
+  one cubic spline per channel along time (``scint_spline_resample_rows``) and the trapezoid stretch (``scint_trap_scale``).
+
+The lmfit-driven fits and plotting are out of scope.
 """
 import functools
 import os
@@ -120,7 +123,13 @@ class Dynspec:
     chunks = DeviceBacked("chunks")          # the retrieved wavefield chunks (1 GB for a 4096^2 observation): in HBM until read
     wavefield = DeviceBacked("wavefield")
     lamdyn = DeviceBacked("lamdyn")
-    acf = DeviceBacked("acf")                # [2 nf, 2 nt]: 512 MB for a 4096^2 observation; the scales read a few cuts of it
+    vdyn = DeviceBacked("vdyn")              # scale_dyn('velocity') / ('trapezoid') and their spectra, parked the same way
+    vlamdyn = DeviceBacked("vlamdyn")
+    trapdyn = DeviceBacked("trapdyn")
+    vsspec = DeviceBacked("vsspec")
+    vlamsspec = DeviceBacked("vlamsspec")
+    trapsspec = DeviceBacked("trapsspec")
+    acf =DeviceBacked("acf")                # [2 nf, 2 nt]: 512 MB for a 4096^2 observation; the scales read a few cuts of it
 
     def __init__(self, filename=None, dyn=None, verbose=True, process=False, lamsteps=False,
                  remove_short_subs=True, subint_thresh=2.33, mjd=None):
@@ -207,21 +216,32 @@ class Dynspec:
 
         Sets ``self.sspec / self.fdop / self.tdel`` (``self.lamsspec`` and ``self.beta`` with
         ``lamsteps``, on the wavelength-scaled spectrum of ``scale_dyn``) or, with ``input_dyn``
-        or ``return_sspec``, returns ``(fdop, yaxis, sec)``.  The velocity- and
-        trapezoid-rescaled variants are outside the hot path and raise ``NotImplementedError``.
+        or ``return_sspec``, returns ``(fdop, yaxis, sec)``.  ``velocity`` takes the velocity-scaled spectrum of
+        ``scale_dyn('velocity', pars=...)`` and sets ``vsspec`` (``vlamsspec`` with ``lamsteps``); ``trap`` rescales
+        to the trapezoid (every time, with scale_dyn's default window, as in the reference) and sets ``trapsspec``.
         """
-        if velocity or trap:
-            raise NotImplementedError("velocity / trap need Dynspec.scale_dyn('velocity'/'trapezoid'), "
-                                      "which is outside the accelerated hot path")
         if plot:
             raise NotImplementedError("plotting is outside the accelerated hot path")
         cls = type(self)
+        target = cls.sspec                                  # where the spectrum goes (dynspec.py:3723-3734)
         if input_dyn is not None:
             dyn_t = to_device(input_dyn, torch.float64)
-        elif lamsteps:
+        elif lamsteps:                                      # dynspec.py:3643-3661
             if not cls.lamdyn.present(self):
                 self.scale_dyn()
-            dyn_t = cls.lamdyn.tensor(self)
+            if velocity:
+                if not cls.vlamdyn.present(self):
+                    self.scale_dyn(scale='velocity')        # (without pars: the ValueError about the parameter dictionary)
+                dyn_t, target = cls.vlamdyn.tensor(self), cls.vlamsspec
+            else:
+                dyn_t, target = cls.lamdyn.tensor(self), cls.lamsspec
+        elif velocity:
+            if not cls.vdyn.present(self):
+                self.scale_dyn(scale='velocity')
+            dyn_t, target = cls.vdyn.tensor(self), cls.vsspec
+        elif trap:
+            self.scale_dyn(scale='trapezoid')               # every time: the reference tests hasattr(self, 'trap'), never set
+            dyn_t, target = cls.trapdyn.tensor(self), cls.trapsspec
         else:
             dyn_t = to_device(self.dyn, torch.float64)
         sec_t = sspec_device(dyn_t, prewhite=prewhite, halve=halve, window=window, window_frac=window_frac)
@@ -235,11 +255,9 @@ class Dynspec:
         if lamsteps:
             beta = np.divide(td, (nrfft * self.dlam))                            # m^-1 (dynspec.py:3703-3704)
         if input_dyn is None and not return_sspec:
+            target.park(self, sec_t)                # copied to the host when first read
             if lamsteps:
-                cls.lamsspec.park(self, sec_t)      # copied to the host when first read
                 self.beta = beta
-            else:
-                cls.sspec.park(self, sec_t)
             self.fdop = fdop
             self.tdel = tdel
             return None
@@ -249,14 +267,25 @@ class Dynspec:
     def scale_dyn(self, scale='lambda', window_frac=0.1, pars=None, parfile=None, window='hanning',
                   spacing='auto', s=None, d=None, vism_ra=None, vism_dec=None, Omega=None, inc=None,
                   vism_zeta=None, zeta=None, lamsteps=False, velocity=False, trap=False):
-        """Rescale the dynamic spectrum (dynspec.py:3872-4080): the equal-wavelength resample
-        (``'lambda'`` / ``'wavelength'`` / ``lamsteps``) runs on the GPU -- one not-a-knot cubic
-        spline per time column -- and sets ``lamdyn / lam / nlam / dlam``.  The velocity, orbit and
-        trapezoid scalings need ephemerides and are outside the accelerated hot path."""
-        if ('velocity' in scale) or ('orbit' in scale) or velocity or ('trapezoid' in scale) or trap:
-            raise NotImplementedError("velocity / orbit / trapezoid scaling is outside the accelerated hot path")
+        """Rescale the dynamic spectrum (dynspec.py:3872-4128) on the GPU; a name that holds several scalings
+        (``'lambda-velocity'``) runs them in this order.
+
+        * ``'lambda'`` / ``'wavelength'`` / ``lamsteps``: the equal-wavelength resample, one not-a-knot cubic spline per
+          time column; sets ``lamdyn / lam / nlam / dlam``.
+        * ``'velocity'`` / ``'orbit'`` / ``velocity``: every channel onto equal steps of the cumulative effective velocity,
+          one cubic spline per channel; needs ``pars`` (or ``parfile``) with RAJ, DECJ, the binary and proper-motion
+          parameters, ``s`` and ``d``; sets ``vdyn`` (``vlamdyn`` when ``lamdyn`` is there), ``veff_ra``, ``veff_dec``.
+          The two ephemeris look-ups (``scint_utils.get_ssb_delay`` / ``get_earth_velocity``) need astropy;
+          ``arcfit.velocity_resample_device`` takes velocities from any other source.
+        * ``'trapezoid'`` / ``trap``: every channel's time axis stretched in proportion to its frequency; sets ``trapdyn``.
+        """
         if ('lambda' in scale) or ('wavelength' in scale) or lamsteps:
             arcfit.scale_dyn_lambda(self, spacing=spacing)
+        if ('velocity' in scale) or ('orbit' in scale) or velocity:
+            arcfit.scale_dyn_velocity(self, pars=pars, parfile=parfile, s=s, d=d, vism_ra=vism_ra, vism_dec=vism_dec,
+                                      Omega=Omega, inc=inc, vism_zeta=vism_zeta, zeta=zeta)
+        if 'trap' in scale or trap:
+            arcfit.scale_dyn_trapezoid(self, window=window, window_frac=window_frac)
 
     norm_sspec = arcfit.norm_sspec
     fit_arc = arcfit.fit_arc
