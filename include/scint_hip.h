@@ -807,6 +807,42 @@ int32_t scint_spline_resample_rows(const double* dyn, int64_t nf, int64_t nt, co
 int32_t scint_trap_scale(const double* dyn, int64_t nf, int64_t nt, double mean, const double* cw, const double* sw,
                          const double* times, const int32_t* nkeep, double* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The any-length 2-D transform and the brightness-distribution model scint_sim.Brightness (scint_sim.py:768-958, after Yao et al.
+ * 2020); kernels in csrc/bright.hpp, DESIGN.md 4o.  All asynchronous on `stream`; no atomics: equal inputs give equal bits.
+ *
+ * scint_fft2_any: the forward 2-D DFT (NumPy's sign) of in[R][C], 2 <= R, C <= 4096 (SCINT_E_ARG otherwise).  A power-of-two
+ *   length the row / column kernels take (rows: 16 .. 8192, columns: >= 2) goes to them; any other length n goes through Bluestein's
+ *   chirp-z at the power of two M >= 2 n - 1 (at least 16; so n <= 4096 with the row kernel's 8192): chirp, zero-pad, forward
+ *   transform, times the chirp filter's transform (formed once per length and cached beside the twiddle tables), inverse transform,
+ *   chirp, crop.  The chirp phase pi k^2 / n comes from k^2 mod 2 n in integers.
+ *   real_input: `in` is float64 [R][C] (else complex128).  in_shift / out_shift: 0 none, 1 np.fft.fftshift, 2 np.fft.ifftshift of
+ *   the input before / the result after the transform (they differ on odd lengths), folded into the index arithmetic.
+ *   out_what: 0 out is complex128 [R][C]; 1 float64 [R][C] = the modulus; 2 float64 [R][C] = the real part.
+ *   Non-finite input propagates as in NumPy.  Workspace: scint_fft2_any_workspace_bytes(R, C).
+ * scint_bright_efield: rho[n][n] = exp(-0.5 * (a X^2 + b Y^2 + c X Y)**alpha2), X = x[column], Y = x[row] (calc_brightness,
+ *   :855-857); a, b, c are the host's (the kernel does not divide by 1 - R^2).
+ * scint_bright_map: per pixel (itd, ifd) of the [ntd][nfd] spectrum the loop body of calc_SS (:911-925) and
+ *   ss0 = B(thetax, thetay) * amp + B(thetax, -thetay) * amp (:933-938), jacobian = amp; thetax / thetay are written when not NULL.
+ *   B(.,.) is scipy's griddata(method='linear') of B[n][n] on the grid x[n] x x[n] (ascending): piecewise linear on the two
+ *   triangles of a cell, NaN outside the grid.  diagonals: bit iy (n - 1) + ix (bit b of byte b / 8 is (byte >> (b % 8)) & 1) says
+ *   that the cell with corners (ix, iy) .. (ix + 1, iy + 1) is split along the diagonal through those two corners, 0 along the
+ *   other; NULL = 1 everywhere.  par (HOST [9]): thetagx, thetagy, thetarx, thetarx**2, thetary**2, 0.5 * df, 2 / df, 10**(-6) and
+ *   (n - 1) / (x[n-1] - x[0]).
+ * scint_bright_fold: ss = ss0 with ss[1:, 1:] += flip(flip(ss0[1:, 1:])), lss = 10 log10(ss) (:947-950); ss must not be ss0.
+ * scint_divide_by_max: x /= np.max(x) in place (calc_acf, :956): NaN if any element is NaN.  Two fixed-order stages.
+ *   Workspace: scint_divide_by_max_workspace_bytes(). */
+int32_t scint_fft2_any_workspace_bytes(int64_t R, int64_t C, size_t* SCINT_HOST bytes);
+int32_t scint_fft2_any(const void* in, int32_t real_input, int64_t R, int64_t C, int32_t in_shift, int32_t out_shift,
+                       int32_t out_what, void* out, void* workspace, size_t workspace_bytes, void* stream);
+int32_t scint_bright_efield(const double* x, int64_t n, double a, double b, double c, double alpha2, double* rho, void* stream);
+int32_t scint_bright_map(const double* B, const double* x, int64_t n, const uint8_t* diagonals, const double* fd, int64_t nfd,
+                         const double* td, int64_t ntd, const double* SCINT_HOST par /*[9]*/, double* ss0, double* jacobian,
+                         double* thetax, double* thetay, void* stream);
+int32_t scint_bright_fold(const double* ss0, int64_t ntd, int64_t nfd, double* ss, double* lss, void* stream);
+int32_t scint_divide_by_max_workspace_bytes(size_t* SCINT_HOST bytes);
+int32_t scint_divide_by_max(double* x, int64_t n, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -312,7 +312,7 @@ __device__ inline int shift_half(int i, int n) {
 }
 
 enum SrcMode { SRC_ARRAY = 0, SRC_SSPEC = 1, SRC_CS = 2, SRC_MODEL = 3, SRC_MULCONJ = 4, SRC_CONJ = 5,
-               SRC_ACF_IN = 6, SRC_POWER = 7, SRC_CPAD = 8, SRC_DBPOWER = 9 };
+               SRC_ACF_IN = 6, SRC_POWER = 7, SRC_CPAD = 8, SRC_DBPOWER = 9, SRC_ROLL = 10 };
 
 // Element (row, j) of the row-FFT input, j in [0, fft length).
 struct RowSource {
@@ -329,6 +329,9 @@ struct RowSource {
     // SRC_MODEL: conj(ifftshift(recov)) -- real(ifft2(x)) == real(fft2(conj x))/(R C)
     // SRC_DBPOWER: 10**(fftshift(sec)/10) of a REAL full-frame spectrum in dB sec[R][C] = wv.dyn (dynspec.py:3802-3803)
     int R, C;
+    // SRC_ROLL: x[(r + roll_r) % R][(j + roll_c) % C] of a real x = wv.dyn (roll_real) or a complex x = a: fftshift is a roll by
+    // n - n/2, ifftshift one by n/2 -- they differ on odd lengths (scint_fft2_any)
+    int roll_r, roll_c, roll_real;
 
     __device__ inline double sspec_d(int r, int c) const { return wv.at(r, c) - m2[0]; }
 
@@ -360,6 +363,14 @@ struct RowSource {
                 break;
             case SRC_CS: v = mk(j < wv.nt ? wv.dyn[(int64_t)r * wv.nt + j] : pad, 0.0); break;
             case SRC_CPAD: v = j < wv.nt ? a[(int64_t)r * wv.nt + j] : mk(0.0, 0.0); break;
+            case SRC_ROLL: {
+                int sr = r + roll_r, sc = j + roll_c;
+                if (sr >= R) sr -= R;
+                if (sc >= C) sc -= C;
+                const int64_t o = (int64_t)sr * C + sc;
+                v = roll_real ? mk(wv.dyn[o], 0.0) : a[o];
+                break;
+            }
             default: {  // SRC_MODEL
                 const int sr = shift_half(r, R), sc = shift_half(j, C);
                 v = conj(a[(int64_t)sr * C + sc]);
@@ -422,7 +433,7 @@ struct ColSourcePlain {
 };
 
 enum SinkMode { SINK_ARRAY = 0, SINK_SSPEC = 1, SINK_CS = 2, SINK_MODEL = 3, SINK_CONJ = 4, SINK_GS_FWD = 5,
-                SINK_GS_INV = 6, SINK_ACF = 7 };
+                SINK_GS_INV = 6, SINK_ACF = 7, SINK_ROLL = 8 };
 
 // Final value at natural frequency (k1 along the strided axis, c along the contiguous one).
 struct ColSink {
@@ -438,6 +449,8 @@ struct ColSink {
     int crop_r, crop_c;                                              // SINK_CONJ: keep [0,crop_r) x [0,crop_c)
     int zero_lo, zero_hi;                                            // SINK_GS_FWD: natural rows to zero
     const double* amp; const uint8_t* pos;                           // SINK_GS_INV: sqrt(dyn), posdspec
+    int roll_r, roll_c, roll_what;                                   // SINK_ROLL: to [(k1 + roll_r) % R][(c + roll_c) % C];
+                                                                     //   0 the value (out_c), 1 its modulus, 2 its real part (out_d)
 
     int half;                   // real input: only columns 0..C/2 are transformed; the rest is
                                 // X[(R-k1)%R, C-c] = conj X[k1, c]
@@ -527,6 +540,15 @@ struct ColSink {
             case SINK_ACF: {   // real(fftshift(ifft2(.)))  (dynspec.py:3793-3795)
                 const int orow = shift_half(k1, R), ocol = shift_half(c, C);
                 out_d[(int64_t)orow * C + ocol] = v.x * scale;
+                break;
+            }
+            case SINK_ROLL: {
+                int orow = k1 + roll_r, ocol = c + roll_c;
+                if (orow >= R) orow -= R;
+                if (ocol >= C) ocol -= C;
+                const int64_t o = (int64_t)orow * C + ocol;
+                if (roll_what == 0) out_c[o] = v;
+                else out_d[o] = roll_what == 1 ? hypot(v.x, v.y) : v.x;
                 break;
             }
             case SINK_GS_FWD:  // CWF[tau < 0] = 0 in natural frequency order (dynspec.py:1869-1870)
@@ -1341,6 +1363,100 @@ extern "C" int32_t scint_acf_sspec(const double* sec_db, int64_t R, int64_t C, i
     const int blocks = (int)std::min<int64_t>(kRedBlocks, std::max<int64_t>(1, ceil_div(R * C, 1024)));
     hipLaunchKernelGGL(max_partial_kernel, dim3(blocks), dim3(256), 0, stream, acf_out, R * C, partial);
     hipLaunchKernelGGL(scale_by_max_kernel, dim3(blocks), dim3(256), 0, stream, acf_out, R * C, partial, blocks);
+    SCINT_LAUNCH_CHECK();
+    return SCINT_OK;
+}
+
+// ------------------------------------------------------------------------------
+// scint_fft2_any and the brightness-distribution model (scint_sim.py:768-958, Brightness): kernels in bright.hpp
+// ------------------------------------------------------------------------------
+#include "bright.hpp"
+
+static bool fft2_any_shape_ok(int64_t R, int64_t C) { return R >= 2 && C >= 2 && R <= 4096 && C <= 4096; }
+// the roll that a shift code stands for along an axis of length n: 0 none, 1 fftshift, 2 ifftshift.  As a SOURCE index
+// (out[i] = x[(i + roll) % n]) fftshift is n - n/2 and ifftshift n/2; as a SINK index (out[(k + roll) % n] = X[k]) the two swap.
+static int fft2_any_roll(int32_t code, int64_t n, bool sink) {
+    if (code == 0) return 0;
+    const int64_t half = n / 2;
+    return (int)(((code == 1) != sink) ? (n - half) % n : half);
+}
+
+extern "C" int32_t scint_fft2_any_workspace_bytes(int64_t R, int64_t C, size_t* bytes) {
+    SCINT_REQUIRE(bytes != nullptr, "fft2_any_workspace_bytes: null output");
+    SCINT_REQUIRE(fft2_any_shape_ok(R, C), "fft2_any_workspace_bytes: each axis must hold 2 .. 4096 points");
+    *bytes = fft2_general_ws(R, C, R) + 256;
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_fft2_any(const void* in, int32_t real_input, int64_t R, int64_t C, int32_t in_shift, int32_t out_shift,
+                                  int32_t out_what, void* out, void* workspace, size_t workspace_bytes, void* stream) {
+    SCINT_REQUIRE(in && out && workspace, "fft2_any: null pointer");
+    // a Bluestein axis of n points runs at the power of two >= 2 n - 1, and the row kernel ends at 8192
+    SCINT_REQUIRE(fft2_any_shape_ok(R, C), "fft2_any: each axis must hold 2 .. 4096 points");
+    SCINT_REQUIRE(in_shift >= 0 && in_shift <= 2 && out_shift >= 0 && out_shift <= 2 && out_what >= 0 && out_what <= 2,
+                  "fft2_any: shifts are 0 (none), 1 (fftshift), 2 (ifftshift); the output 0 (complex), 1 (modulus), 2 (real part)");
+    RowSource src{};
+    src.mode = SRC_ROLL; src.R = (int)R; src.C = (int)C; src.roll_real = real_input != 0;
+    src.wv.dyn = (const double*)in; src.a = (const cplx*)in;
+    src.roll_r = fft2_any_roll(in_shift, R, false); src.roll_c = fft2_any_roll(in_shift, C, false);
+    ColSink sink{};
+    sink.mode = SINK_ROLL; sink.out_c = (cplx*)out; sink.out_d = (double*)out; sink.roll_what = out_what;
+    sink.roll_r = fft2_any_roll(out_shift, R, true); sink.roll_c = fft2_any_roll(out_shift, C, true);
+    return fft2_general(src, R, 0.0, R, C, sink, workspace, workspace_bytes, (hipStream_t)stream, real_input != 0);
+}
+
+extern "C" int32_t scint_bright_efield(const double* x, int64_t n, double a, double b, double c, double alpha2, double* rho,
+                                       void* stream) {
+    SCINT_REQUIRE(x && rho, "bright_efield: null pointer");
+    SCINT_REQUIRE(n >= 2 && n <= 32768, "bright_efield: the grid must hold 2 .. 32768 points a side");
+    hipLaunchKernelGGL(bright_efield_kernel, dim3((unsigned)ceil_div(n * n, 256)), dim3(256), 0, (hipStream_t)stream, x, (int)n, a, b,
+                       c, alpha2, rho);
+    SCINT_LAUNCH_CHECK();
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_bright_map(const double* B, const double* x, int64_t n, const uint8_t* diagonals, const double* fd,
+                                    int64_t nfd, const double* td, int64_t ntd, const double* par, double* ss0, double* jacobian,
+                                    double* thetax, double* thetay, void* stream) {
+    SCINT_REQUIRE(B && x && fd && td && par && ss0 && jacobian, "bright_map: null pointer");
+    SCINT_REQUIRE(n >= 2 && n <= 32768, "bright_map: the grid must hold 2 .. 32768 points a side");
+    SCINT_REQUIRE(nfd >= 1 && ntd >= 1 && nfd < (1 << 30) && ntd < (1 << 30) && ceil_div(nfd * ntd, 256) < (int64_t(1) << 31),
+                  "bright_map: bad spectrum shape");
+    BrightMapPar p;
+    p.B = B; p.x = x; p.n = (int)n; p.diag = diagonals; p.fd = fd; p.nfd = (int)nfd; p.td = td; p.ntd = (int)ntd;
+    p.thetagx = par[0]; p.thetagy = par[1]; p.thetarx = par[2]; p.rx2 = par[3]; p.ry2 = par[4];
+    p.half_df = par[5]; p.two_over_df = par[6]; p.floor_amp = par[7]; p.inv_step = par[8];
+    p.ss0 = ss0; p.jac = jacobian; p.thetax = thetax; p.thetay = thetay;
+    hipLaunchKernelGGL(bright_map_kernel, dim3((unsigned)ceil_div(nfd * ntd, 256)), dim3(256), 0, (hipStream_t)stream, p);
+    SCINT_LAUNCH_CHECK();
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_bright_fold(const double* ss0, int64_t ntd, int64_t nfd, double* ss, double* lss, void* stream) {
+    SCINT_REQUIRE(ss0 && ss && lss && ss != ss0, "bright_fold: null pointer, or folding in place");
+    SCINT_REQUIRE(nfd >= 1 && ntd >= 1 && nfd < (1 << 30) && ntd < (1 << 30) && ceil_div(nfd * ntd, 256) < (int64_t(1) << 31),
+                  "bright_fold: bad spectrum shape");
+    hipLaunchKernelGGL(bright_fold_kernel, dim3((unsigned)ceil_div(nfd * ntd, 256)), dim3(256), 0, (hipStream_t)stream, ss0, (int)ntd,
+                       (int)nfd, ss, lss);
+    SCINT_LAUNCH_CHECK();
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_divide_by_max_workspace_bytes(size_t* bytes) {
+    SCINT_REQUIRE(bytes != nullptr, "divide_by_max_workspace_bytes: null output");
+    *bytes = sizeof(double) * (kRedBlocks + 8);
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_divide_by_max(double* x, int64_t n, void* workspace, size_t workspace_bytes, void* stream_) {
+    SCINT_REQUIRE(x && workspace && n >= 1 && ceil_div(n, 256) < (int64_t(1) << 31), "divide_by_max: null pointer or bad length");
+    if (workspace_bytes < sizeof(double) * (kRedBlocks + 8)) { set_error("scint: divide_by_max workspace too small"); return SCINT_E_WORKSPACE; }
+    hipStream_t stream = (hipStream_t)stream_;
+    double* partial = (double*)workspace;
+    const int blocks = (int)std::min<int64_t>(kRedBlocks, std::max<int64_t>(1, ceil_div(n, 1024)));
+    hipLaunchKernelGGL(bright_max_partial_kernel, dim3(blocks), dim3(256), 0, stream, x, n, partial);
+    hipLaunchKernelGGL(bright_max_final_kernel, dim3(1), dim3(64), 0, stream, partial, blocks);
+    hipLaunchKernelGGL(bright_divide_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, stream, x, n, partial + blocks);
     SCINT_LAUNCH_CHECK();
     return SCINT_OK;
 }

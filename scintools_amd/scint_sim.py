@@ -28,6 +28,16 @@ raises ``NotImplementedError`` otherwise.
 
 Its Fresnel sums run as one float64 matrix-core contraction per frequency lag (csrc/acf.hpp, entry point scint_acf_model;
 DESIGN.md, "The 2-D ACF model"); the axes, the ``dnun = 0`` column and the mirroring are the reference's NumPy lines on the host.
+
+``Brightness`` is the reference's brightness-distribution model of a secondary spectrum and its ACF (scint_sim.py:768-958; Yao et
+al. 2020):
+
+    from scintools_amd.scint_sim import Brightness
+    b = Brightness(ar=2, psi=30, thetagx=0.5, thetarx=0.5)       # b.SS, b.acf, ...
+
+The field ACF, the per-pixel map with both interpolations of the brightness, the fold and the ACF's normalisation are kernels of
+csrc/bright.hpp; its transforms have whatever lengths ``np.arange`` gives and go through ``fft2_any`` (scint_fft2_any: Bluestein's
+chirp-z where a length is not a power of two; DESIGN.md, "The brightness-distribution model").
 """
 import ctypes
 import warnings
@@ -413,3 +423,232 @@ class ACF:
 
     def plot_sspec(self, *args, **kwargs):
         warnings.warn("ACF.plot_sspec: plotting is outside the accelerated hot path; nothing is drawn")
+
+
+FFT_ANY_MAX = 4096        # a Bluestein axis of n points runs at the power of two >= 2 n - 1; the row kernel ends at 8192
+
+
+def fft2_any(a, in_shift=None, out_shift=None, out="complex"):
+    """``np.fft.fft2`` of a 2-D float64 or complex128 array (NumPy or device tensor) of any lengths 2 .. 4096 on the device
+    (scint_fft2_any: Bluestein's chirp-z where a length is not one the power-of-two kernels take).  ``in_shift`` / ``out_shift``:
+    None, 'fftshift' or 'ifftshift' applied to the input / the result; ``out``: 'complex', 'abs' or 'real'.  Returns a device tensor."""
+    dev = device.require_gpu()
+    real = not (a.is_complex() if isinstance(a, torch.Tensor) else np.iscomplexobj(a))
+    if len(a.shape) != 2:
+        raise ValueError(f"fft2_any: a 2-D array is needed, got {len(a.shape)} dimensions")
+    R, C = (int(n) for n in a.shape)
+    for n in (R, C):
+        if not 2 <= n <= FFT_ANY_MAX:
+            raise ValueError(f"fft2_any: an axis of {n} points; the device transform takes 2 .. {FFT_ANY_MAX} "
+                             f"(an arbitrary length n runs at the power of two >= 2 n - 1, at most 8192)")
+    shifts = {None: 0, "fftshift": 1, "ifftshift": 2}
+    what = {"complex": 0, "abs": 1, "real": 2}[out]
+    src = device.to_device(a, torch.float64 if real else torch.complex128)
+    res = torch.empty((R, C), dtype=torch.complex128 if what == 0 else torch.float64, device=dev)
+    ws = device.workspace_for("scint_fft2_any", R, C)
+    _lib.call("scint_fft2_any", src, int(real), R, C, shifts[in_shift], shifts[out_shift], what, res, ws, ws.numel(),
+              device.stream_ptr())
+    return res
+
+
+def diagonals_from_simplices(simplices, n):
+    """The one bit per cell of a triangulation of the regular ``n x n`` grid (point ``iy * n + ix``): bool ``[n-1, n-1]``, True where
+    cell ``(iy, ix)`` is split along the diagonal from corner ``(ix, iy)`` to ``(ix+1, iy+1)``.  Raises ``ValueError`` unless every
+    simplex lies inside one cell and every cell holds exactly two simplices that share one diagonal -- it does not guess."""
+    s = np.asarray(simplices)
+    if s.ndim != 2 or s.shape[1] != 3:
+        raise ValueError(f"diagonals_from_simplices: simplices of shape {s.shape}, expected [ntri, 3]")
+    iy, ix = np.divmod(s, n)
+    y0, x0 = iy.min(axis=1), ix.min(axis=1)
+    if np.any(s < 0) or np.any(s >= n * n) or np.any(iy.max(axis=1) - y0 != 1) or np.any(ix.max(axis=1) - x0 != 1):
+        raise ValueError("diagonals_from_simplices: a simplex does not lie inside one grid cell")
+    corner = 2 * (iy - y0[:, None]) + (ix - x0[:, None])                 # 0 .. 3: (0,0), (1,0), (0,1), (1,1) as (dx, dy)
+    has = np.zeros((len(s), 4), dtype=bool)
+    has[np.arange(len(s))[:, None], corner] = True
+    if np.any(has.sum(axis=1) != 3):
+        raise ValueError("diagonals_from_simplices: a simplex repeats a vertex")
+    main = has[:, 0] & has[:, 3]                                          # otherwise it holds corners 1 and 2: the other diagonal
+    cell = y0 * (n - 1) + x0
+    count = np.bincount(cell, minlength=(n - 1) ** 2)
+    nmain = np.bincount(cell, weights=main, minlength=(n - 1) ** 2)
+    if len(count) != (n - 1) ** 2 or np.any(count != 2):
+        raise ValueError("diagonals_from_simplices: not every cell holds exactly two simplices")
+    if np.any((nmain != 0) & (nmain != 2)):
+        raise ValueError("diagonals_from_simplices: the two simplices of a cell do not share a diagonal")
+    return (nmain == 2).reshape(n - 1, n - 1)
+
+
+def qhull_diagonals(x):
+    """The diagonals of the triangulation ``scipy.interpolate.griddata(method='linear')`` builds for the grid ``meshgrid(x, x)``:
+    ``scipy.spatial.Delaunay`` of the same points with the same (default) options."""
+    from scipy.spatial import Delaunay
+    X, Y = np.meshgrid(x, x)
+    tri = Delaunay(np.column_stack((np.ravel(X), np.ravel(Y))))
+    return diagonals_from_simplices(tri.simplices, len(x))
+
+
+class Brightness:
+    """The reference's ``Brightness`` (scint_sim.py:768-958; Yao et al. 2020): the secondary spectrum, and its ACF, of an anisotropic
+    Kolmogorov brightness distribution with phase-gradient offsets.  Same arguments, methods (``calc_brightness``, ``calc_SS``,
+    ``calc_acf``) and attributes (``x, X, Y, acf_efield, B, fd, td, thetax, thetay, jacobian, SS, LSS, acf``).
+
+        b = Brightness(ar=2, psi=30, thetagx=0.5, thetarx=0.5)
+        b.SS, b.acf
+
+    The axes are ``np.arange`` on the host.  ``acf_efield, B, SS, LSS, acf, jacobian`` stay in device memory until first read;
+    ``thetax`` and ``thetay`` (and ``X``, ``Y``) are produced on first access.  ``plot=True`` and the ``plot_*`` methods warn and draw nothing.
+
+    The reference interpolates ``B`` with ``scipy.interpolate.griddata(method='linear')``: piecewise linear on a Delaunay
+    triangulation that splits every grid cell along one of its diagonals -- which one is Qhull's tie-break.
+    ``triangulation='qhull'`` (default) takes that bit per cell from ``scipy.spatial.Delaunay`` of the grid (the reference's result on the
+    same scipy; the triangulation is the slow part); ``'main'`` splits every cell along the same diagonal and needs no scipy (for fits
+    and large grids).  ``diagonals`` (bool ``[n-1, n-1]``, see ``diagonals_from_simplices``) overrides both.
+    Every transform goes through ``fft2_any``: the grid and both axes of the spectrum hold at most 4096 points (``ValueError``)."""
+
+    acf_efield = device.DeviceBacked("acf_efield")
+    B = device.DeviceBacked("B")
+    SS = device.DeviceBacked("SS")
+    LSS = device.DeviceBacked("LSS")
+    jacobian = device.DeviceBacked("jacobian")
+    acf = device.DeviceBacked("acf")
+
+    def __init__(self, ar=1.0, psi=0, alpha=1.67, thetagx=0, thetagy=0, thetarx=0, thetary=0, df=0.02, dt=0.08, dx=0.1, nf=10,
+                 nt=80, nx=30, ncuts=5, plot=False, contour=True, figsize=(10, 8), calc_sspec=True, calc_acf=True,
+                 triangulation="qhull", diagonals=None):
+        if triangulation not in ("qhull", "main"):
+            raise ValueError(f"triangulation={triangulation!r}: 'qhull' or 'main'")
+        self.ar = ar
+        self.alpha = alpha
+        self.thetagx = thetagx
+        self.thetagy = thetagy
+        self.thetarx = thetarx
+        self.thetary = thetary
+        self.psi = psi
+        self.df = df
+        self.dt = dt
+        self.dx = dx
+        self.nf = nf
+        self.nt = nt
+        self.nx = nx
+        self.ncuts = ncuts
+        self.triangulation = triangulation
+        self.diagonals = None if diagonals is None else np.asarray(diagonals)
+        self.calc_brightness()
+        if plot:
+            self.plot_acf_efield(figsize=figsize)
+            self.plot_brightness(figsize=figsize)
+        if calc_sspec:
+            self.calc_SS()
+            if plot:
+                self.plot_sspec(figsize=figsize)
+                self.plot_cuts(figsize=figsize)
+        if calc_acf:
+            self.calc_acf()
+            if plot:
+                self.plot_acf(figsize=figsize, contour=contour)
+
+    @staticmethod
+    def _check_axis(name, n):
+        if not 2 <= n <= FFT_ANY_MAX:
+            raise ValueError(f"Brightness: {name} holds {n} points; the device transform takes 2 .. {FFT_ANY_MAX}")
+
+    def calc_brightness(self):
+        """``acf_efield`` and ``B = |ifftshift(fft2(fftshift(acf_efield)))|`` (scint_sim.py:838-869)."""
+        dev = device.require_gpu()
+        x = np.arange(-self.nx, self.nx, self.dx)
+        n = len(x)
+        self._check_axis("the grid x = arange(-nx, nx, dx)", n)
+        if self.diagonals is not None and (self.diagonals.shape != (n - 1, n - 1) or self.diagonals.dtype != np.bool_):
+            raise ValueError(f"diagonals: a bool array of shape {(n - 1, n - 1)} is needed for the grid of {n} points, "
+                             f"got {self.diagonals.dtype} {self.diagonals.shape}")
+        R = (self.ar**2 - 1) / (self.ar**2 + 1)
+        cosa = np.cos(2 * (90 - self.psi) * np.pi / 180)
+        sina = np.sin(2 * (90 - self.psi) * np.pi / 180)
+        a = (1 - R * cosa) / np.sqrt(1 - R**2)
+        b = (1 + R * cosa) / np.sqrt(1 - R**2)
+        c = -2 * R * sina / np.sqrt(1 - R**2)
+        self.x = x
+        for stale in ("_bits", "X", "Y"):
+            self.__dict__.pop(stale, None)
+        self._x_t = device.to_device(x, torch.float64)
+        rho = torch.empty((n, n), dtype=torch.float64, device=dev)
+        _lib.call("scint_bright_efield", self._x_t, n, float(a), float(b), float(c), float(self.alpha / 2), rho, device.stream_ptr())
+        type(self).acf_efield.park(self, rho)
+        type(self).B.park(self, fft2_any(rho, in_shift="fftshift", out_shift="ifftshift", out="abs"))
+
+    def _diagonal_bits(self):
+        """The packed bitmap scint_bright_map reads (device uint8), or None for the same diagonal everywhere."""
+        diag = self.diagonals
+        if diag is None:
+            if self.triangulation == "main":
+                return None
+            diag = qhull_diagonals(self.x)
+        return device.to_device(np.packbits(np.ravel(diag), bitorder="little"), torch.uint8)
+
+    def _map(self, want_theta):
+        dev = device.require_gpu()
+        fd, td = self.fd, self.td
+        shape = (len(td), len(fd))
+        n = len(self.x)
+        if "_bits" not in self.__dict__:
+            self._bits = self._diagonal_bits()
+        par = np.array([self.thetagx, self.thetagy, self.thetarx, self.thetarx**2, self.thetary**2, 0.5 * self.df, 2 / self.df,
+                        10**(-6), (n - 1) / (self.x[-1] - self.x[0])], dtype=np.float64)
+        out = [torch.empty(shape, dtype=torch.float64, device=dev) for _ in range(4 if want_theta else 2)]
+        _lib.call("scint_bright_map", type(self).B.tensor(self), self._x_t, n, self._bits, device.to_device(fd, torch.float64),
+                  len(fd), device.to_device(td, torch.float64), len(td), par, out[0], out[1],
+                  out[2] if want_theta else None, out[3] if want_theta else None, device.stream_ptr())
+        return out
+
+    def calc_SS(self):
+        """``SS``, ``LSS`` and ``jacobian`` (scint_sim.py:871-951): the loop body, both interpolations and the fold on the device."""
+        dev = device.require_gpu()
+        self.fd = np.arange(-self.nf, self.nf, self.df)
+        self.td = np.arange(-self.nt, self.nt, self.dt)
+        ntd, nfd = len(self.td), len(self.fd)
+        if ntd < 1 or nfd < 1:
+            raise ValueError(f"Brightness: an empty spectrum ({ntd} x {nfd})")
+        self.__dict__.pop("thetax", None)
+        self.__dict__.pop("thetay", None)
+        ss0, jac = self._map(False)
+        ss = torch.empty_like(ss0)
+        lss = torch.empty_like(ss0)
+        _lib.call("scint_bright_fold", ss0, ntd, nfd, ss, lss, device.stream_ptr())
+        type(self).jacobian.park(self, jac)
+        type(self).SS.park(self, ss)
+        type(self).LSS.park(self, lss)
+
+    def calc_acf(self):
+        """``acf = real(fftshift(fft2(fftshift(SS))))`` over its ``np.max`` (scint_sim.py:953-958)."""
+        ntd, nfd = type(self).SS.shape(self)
+        self._check_axis("the delay axis td = arange(-nt, nt, dt)", ntd)
+        self._check_axis("the Doppler axis fd = arange(-nf, nf, df)", nfd)
+        acf = fft2_any(type(self).SS.tensor(self), in_shift="fftshift", out_shift="fftshift", out="real")
+        ws = device.workspace_for("scint_divide_by_max")
+        _lib.call("scint_divide_by_max", acf, acf.numel(), ws, ws.numel(), device.stream_ptr())
+        type(self).acf.park(self, acf)
+
+    def __getattr__(self, name):                                         # thetax / thetay / X / Y: produced on first access
+        if name in ("thetax", "thetay") and "fd" in self.__dict__:
+            _, _, thx, thy = self._map(True)
+            self.__dict__["thetax"], self.__dict__["thetay"] = thx.cpu().numpy(), thy.cpu().numpy()
+            return self.__dict__[name]
+        if name in ("X", "Y") and "x" in self.__dict__:
+            self.__dict__["X"], self.__dict__["Y"] = np.meshgrid(self.x, self.x)
+            return self.__dict__[name]
+        raise AttributeError(f"'{type(self).__name__}' object has no attribute '{name}'")
+
+    def plot_acf_efield(self, *args, **kwargs):
+        warnings.warn("Brightness.plot_acf_efield: plotting is outside the accelerated hot path; nothing is drawn")
+
+    def plot_brightness(self, *args, **kwargs):
+        warnings.warn("Brightness.plot_brightness: plotting is outside the accelerated hot path; nothing is drawn")
+
+    def plot_sspec(self, *args, **kwargs):
+        warnings.warn("Brightness.plot_sspec: plotting is outside the accelerated hot path; nothing is drawn")
+
+    def plot_acf(self, *args, **kwargs):
+        warnings.warn("Brightness.plot_acf: plotting is outside the accelerated hot path; nothing is drawn")
+
+    def plot_cuts(self, *args, **kwargs):
+        warnings.warn("Brightness.plot_cuts: plotting is outside the accelerated hot path; nothing is drawn")
