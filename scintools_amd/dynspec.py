@@ -453,15 +453,14 @@ class Dynspec:
                           "pass arrays=True for the curve and the fit")
         cf, ct = min(cf, self.ncf_fit - 1), min(ct, self.nct_fit - 1)
         fs, ts = self._chunk(cf, ct)
-        time2, freq2 = self.times[ts], self.freqs[fs]
-        tau = thth.fft_axis(freq2, 1.0, self.npad)
-        fd = thth.fft_axis(time2, 1000.0, self.npad)
+        freq2 = self.freqs[fs]
+        edges = self.edges * (freq2.mean() / self.fref)
+        tau, fd = thth._chunk_axes(self.times[ts], freq2, edges, self.npad)[3:]
         dspec2 = np.copy(self.dyn[fs, ts])
         dspec2 -= np.nanmean(dspec2)
         cs = thth.conjugate_spectrum(np.nan_to_num(dspec2), self.npad, tau, self.thth_tau_mask,
                                      self.thetatheta_proc != 'incoherent', pad_value=0.0)
         etas = self._chunk_etas(freq2)
-        edges = self.edges * (freq2.mean() / self.fref)
         if self.thetatheta_proc == 'thin':
             # scaled to the chunk BEFORE the arclet filter here (dynspec.py:1590-1596), after it in fit_thetatheta
             eigs = thth.sv_sweep_multi(cs.unsqueeze(0), [(tau, fd, edges, edges[np.abs(edges) < self.arclet_lim])], [etas],
@@ -479,7 +478,7 @@ class Dynspec:
         coher = (self.thetatheta_proc != 'incoherent')
         thin = self.thetatheta_proc == 'thin'
         R, C = (self.npad + 1) * self.cwf, (self.npad + 1) * self.cwt
-        per_group = max(1, int((8 << 30) // (16 * R * C)))
+        per_group = thth._group_size(16 * R * C)
         rows = np.full((len(group_all), 2 + self.neta), np.nan)
         for g0 in range(0, len(group_all), per_group):
             group = group_all[g0:g0 + per_group]
@@ -490,8 +489,7 @@ class Dynspec:
             d_all = np.empty((len(group), self.cwf, self.cwt))
             for k, (cf, ct) in enumerate(group):
                 dspec2, freq2, time2, etas, edges = self._search_params(cf, ct)[:5]
-                fd = thth.fft_axis(time2, 1000.0, self.npad)          # ththmod.py:773
-                tau = thth.fft_axis(freq2, 1.0, self.npad)            # ththmod.py:774
+                tau, fd = thth._chunk_axes(time2, freq2, edges, self.npad)[3:]      # ththmod.py:773-774
                 d_all[k] = dspec2
                 pads.append(float(d_all[k].mean()))                   # the padding value (ththmod.py:783)
                 grids.append((tau, fd, edges))
@@ -603,6 +601,18 @@ class Dynspec:
         self.ththetaerr = A_err / self.fref**2
 
     # ------------------------------------------------------------------ phase retrieval
+    def _retrieval_chunks(self):
+        """(cf, ct, fs, ts, freq2, eta, edges) of every half-overlapping retrieval chunk, frequency rows outermost
+        (dynspec.py:1777-1800): its slices, its channels, the fitted curvature and the edges scaled to its mean frequency."""
+        for cf in range(self.ncf_ret):
+            fs = slice(cf * (self.cwf // 2), cf * (self.cwf // 2) + self.cwf)
+            freq2 = np.copy(self.freqs[fs])
+            freq = freq2.mean()
+            eta = self.ththeta * (self.fref / freq)**2
+            for ct in range(self.nct_ret):
+                ts = slice(ct * (self.cwt // 2), ct * (self.cwt // 2) + self.cwt)
+                yield cf, ct, fs, ts, freq2, eta, self.edges * (freq / self.fref)
+
     def thetatheta_chunks(self, verbose=False, pool=None, memmap=False):
         """theta-theta phase retrieval on all half-overlapping chunks (dynspec.py:1765-1826):
         fills ``self.chunks[ncf_ret, nct_ret, cwf, cwt]``.
@@ -617,19 +627,11 @@ class Dynspec:
         if pool is not None:
             self.chunks = np.zeros((self.ncf_ret, self.nct_ret, self.cwf, self.cwt), dtype=complex)
             pars = []
-            for cf in range(self.ncf_ret):
-                fs = slice(cf * (self.cwf // 2), cf * (self.cwf // 2) + self.cwf)
-                freq2 = np.copy(self.freqs[fs])
-                freq = freq2.mean()
-                eta = self.ththeta * (self.fref / freq)**2
-                for ct in range(self.nct_ret):
-                    ts = slice(ct * (self.cwt // 2), ct * (self.cwt // 2) + self.cwt)
-                    time2 = np.copy(self.times[ts])
-                    dspec2 = np.copy(self.dyn[fs, ts])
-                    dspec2 -= np.nanmean(dspec2)
-                    dspec2 = np.nan_to_num(dspec2)
-                    pars.append((dspec2, self.edges * (freq / self.fref), time2, freq2, eta, ct, cf, self.npad,
-                                 self.thth_tau_mask, verbose))
+            for cf, ct, fs, ts, freq2, eta, edges in self._retrieval_chunks():
+                dspec2 = np.copy(self.dyn[fs, ts])
+                dspec2 -= np.nanmean(dspec2)
+                dspec2 = np.nan_to_num(dspec2)
+                pars.append((dspec2, edges, np.copy(self.times[ts]), freq2, eta, ct, cf, self.npad, self.thth_tau_mask, verbose))
             for res in pool.map(thth.single_chunk_retrieval, pars):
                 self.chunks[res[1], res[2], :, :] = res[0]
             return
@@ -637,15 +639,9 @@ class Dynspec:
         # the padding value in NumPy's own summation order: ththmod.chunk_cut_device) and the retrieved chunks stay there for the
         # mosaic -- the host loop above copied 0.5 GB up and 1 GB down and spent 0.2 s in nanmean / nan_to_num of 961 windows.
         pars, origins = [], []
-        for cf in range(self.ncf_ret):
-            fs = slice(cf * (self.cwf // 2), cf * (self.cwf // 2) + self.cwf)
-            freq2 = np.copy(self.freqs[fs])
-            freq = freq2.mean()
-            eta = self.ththeta * (self.fref / freq)**2
-            for ct in range(self.nct_ret):
-                ts = slice(ct * (self.cwt // 2), ct * (self.cwt // 2) + self.cwt)
-                pars.append((None, self.edges * (freq / self.fref), np.copy(self.times[ts]), freq2, eta))
-                origins.append((cf * (self.cwf // 2), ct * (self.cwt // 2)))
+        for cf, ct, fs, ts, freq2, eta, edges in self._retrieval_chunks():
+            pars.append((None, edges, np.copy(self.times[ts]), freq2, eta))
+            origins.append((fs.start, ts.start))
         dyn_h = np.asarray(self.dyn, dtype=float)
         dyn_t = thth.to_device(dyn_h, torch.float64)
         d_t, pad_t = thth.chunk_cut_device(dyn_t, origins, self.cwf, self.cwt, fortran_order=_walks_columns(dyn_h))

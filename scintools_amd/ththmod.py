@@ -196,6 +196,78 @@ def _eta_float(eta):
     return float(units.strip(eta, "eta", "s3", warn=False))
 
 
+# ---- what every entry point does with a chunk (dspec2, edges, time, freq, eta) before anything reaches the device
+def _chunk_strip(time, freq, edges, names=("time2", "freq2")):
+    """(time [s], freq [MHz], edges [mHz]) of a chunk as plain floats; `names`: what a unit error calls time and freq."""
+    return (units.strip(time, names[0], "s", warn=False), units.strip(freq, names[1], "MHz", warn=False),
+            units.strip(edges, "edges", "mHz", warn=False))
+
+
+def _chunk_axes(time, freq, edges, npad, names=("time2", "freq2")):
+    """(time_v, freq_v, edges_v, tau [us], fd [mHz]): a chunk's axes and edges as plain floats and the conjugate axes of the
+    chunk padded `npad` times (ththmod.py:773-774)."""
+    time_v, freq_v, edges_v = _chunk_strip(time, freq, edges, names)
+    return time_v, freq_v, edges_v, fft_axis(freq_v, 1.0, npad), fft_axis(time_v, 1000.0, npad)
+
+
+def _chunk_grid(time, freq, edges, npad, cache=None):
+    """The _Grid of a chunk.  `cache` (a dict; None: a fresh grid): chunks with equal axes and edges -- those of one frequency
+    row -- get ONE object.  961 grid objects were 45 ms of a 0.23-s calc_wavefield before any GPU work was queued, and
+    :func:`_multi_keep_dev` and :func:`_reduced_centres_cached` recognise a shared grid by its id.  The objects are read-only to
+    their users (axes, centres, geometry).  The key does not hold `npad`: a cache serves one call."""
+    time_v, freq_v, edges_v = _chunk_strip(time, freq, edges)
+    # (fft_axis reads only the length and the first step of an axis)
+    key = (time_v.shape[0], float(time_v[1] - time_v[0]), freq_v.shape[0], float(freq_v[1] - freq_v[0]), edges_v.tobytes())
+    grid = None if cache is None else cache.get(key)
+    if grid is None:
+        grid = _Grid(fft_axis(freq_v, 1.0, npad), fft_axis(time_v, 1000.0, npad), edges_v)
+        if cache is not None:
+            cache[key] = grid
+    return grid
+
+
+def _tau_mask_rows(tau_v, tauMask):
+    """Rows [lo, hi) of the conjugate spectrum that the delay mask |tau| < tauMask clears (ththmod.py:785); (0, 0) for none."""
+    sel = np.nonzero(np.abs(tau_v) < float(units.strip(tauMask, "tauMask", "us", warn=False)))[0]
+    if not sel.size:
+        return 0, 0
+    lo, hi = int(sel[0]), int(sel[-1]) + 1
+    if hi - lo != sel.size:
+        raise ValueError("tau mask is not a contiguous block of delays")
+    return lo, hi
+
+
+def _tau_mask_lohi(grids, tauMask):
+    """:func:`_tau_mask_rows` of every chunk of a group as int64 [n, 2], worked out once per distinct grid object."""
+    rows = {}
+    for g in grids:
+        if id(g) not in rows:
+            rows[id(g)] = _tau_mask_rows(g.tau, tauMask)
+    return np.array([rows[id(g)] for g in grids], dtype=np.int64).reshape(len(grids), 2)
+
+
+def _reduced_centres_cached(grid, keep, cache):
+    """Centres of the reduced edges of crop `keep` (ththmod.py:204-205 applied to :157-172).  A crop that is one run of centres
+    is kept in `cache` (a dict) per (grid object, first centre, count): the chunks of a frequency row share it."""
+    n = int(keep.shape[0])
+    key = (id(grid), int(keep[0]), n) if n == int(keep[-1]) - int(keep[0]) + 1 else None
+    th_red = cache.get(key) if key is not None else None
+    if th_red is None:
+        th_red = _theta_centres(grid.edges_red(keep))
+        if key is not None:
+            cache[key] = th_red
+    return th_red
+
+
+RETRIEVAL_GROUP_BYTES = 8 << 30   # device bytes a group of chunks may hold at once: the fit's and the retrievals' stacks of conjugate spectra
+
+
+def _group_size(bytes_per_chunk, group_bytes=None, cap=None):
+    """Chunks per group: as many as fit into `group_bytes` (None or 0: RETRIEVAL_GROUP_BYTES), at least one, at most `cap`."""
+    n = max(1, int((group_bytes or RETRIEVAL_GROUP_BYTES) // bytes_per_chunk))
+    return n if cap is None else min(cap, n)
+
+
 # ----------------------------------------------------------------------------
 # device-level building blocks (torch tensors in, torch tensors out)
 # ----------------------------------------------------------------------------
@@ -819,14 +891,7 @@ def conjugate_spectrum(dspec, npad, tau=None, tau_mask=0.0, coher=True, pad_valu
         _lib.call("scint_mean", d_t, nf * nt, m, stream_ptr())
         pad_value = m.value
     R = (npad + 1) * nf
-    lo = hi = 0
-    if tau is not None:
-        tau_v = units.strip(tau, "tau", "us", warn=False)
-        sel = np.nonzero(np.abs(tau_v) < float(units.strip(tau_mask, "tauMask", "us", warn=False)))[0]
-        if sel.size:
-            lo, hi = int(sel[0]), int(sel[-1]) + 1
-            if hi - lo != sel.size:
-                raise ValueError("tau mask is not a contiguous block of delays")
+    lo, hi = (0, 0) if tau is None else _tau_mask_rows(units.strip(tau, "tau", "us", warn=False), tau_mask)
     ws = workspace_for("scint_cs", nf, nt, npad)
     cs_t = empty((R, (npad + 1) * nt), torch.complex128) if out is None else out
     if tuple(cs_t.shape) != (R, (npad + 1) * nt) or cs_t.dtype != torch.complex128 or not cs_t.is_contiguous():
@@ -868,12 +933,8 @@ def single_search(params):
     warning.  Returns (eta_fit, eta_sig, freq.mean(), time.mean(), eigs).
     """
     (dspec2, freq, time, etas, edges, name, plot, fw, npad, coher, tauMask, verbose) = params
-    time_v = units.strip(time, "time", "s", warn=False)
-    freq_v = units.strip(freq, "freq", "MHz", warn=False)
+    time_v, freq_v, edges_v, tau, fd = _chunk_axes(time, freq, edges, npad, ("time", "freq"))
     etas_v = units.strip(etas, "etas", "s3", warn=False)
-    edges_v = units.strip(edges, "edges", "mHz", warn=False)
-    fd = fft_axis(time_v, 1000.0, npad)          # ththmod.py:773
-    tau = fft_axis(freq_v, 1.0, npad)            # ththmod.py:774
     cs_t = conjugate_spectrum(dspec2, npad, tau, tauMask, coher)
     eigs = eval_sweep(cs_t, tau, fd, etas_v, edges_v)
     eta_fit, eta_sig, _ = fit_eig_peak(etas_v, eigs, fw)
@@ -921,9 +982,6 @@ def _wavefield_from_eigpair(grid, e, keep, V, w, shape, row_t=None, th_t=None):
     return _ifft2_shifted_dev(recov_E, scale=nf * nt / 4, crop=(nf, nt))
 
 
-RETRIEVAL_GROUP_BYTES = 8 << 30   # device bytes of conjugate spectra stacked per retrieval group (the rule of Dynspec._fit_chunks)
-
-
 def chunk_retrieval_batch(chunks, npad, tauMask, verbose=False, group_bytes=None, dev_chunks=None, dev_pads=None, out_device=False):
     """Phase retrieval of MANY chunks of one shape (Dynspec.thetatheta_chunks, dynspec.py:1765-1826): the chunks'
     conjugate spectra in one device stack, all their dominant eigenpairs in ONE batched sweep
@@ -944,7 +1002,7 @@ def chunk_retrieval_batch(chunks, npad, tauMask, verbose=False, group_bytes=None
     ``out_device``: return the device tensor instead of copying a gigabyte of chunks to the host (the mosaic reads them there)."""
     nf, nt = (int(v) for v in dev_chunks.shape[1:]) if dev_chunks is not None else np.asarray(chunks[0][0]).shape
     R, C = (npad + 1) * nf, (npad + 1) * nt
-    per_group = max(1, int((RETRIEVAL_GROUP_BYTES if group_bytes is None else group_bytes) // (16 * R * C)))
+    per_group = _group_size(16 * R * C, group_bytes)
     dev = require_gpu()
     out = torch.zeros((len(chunks), nf, nt), dtype=torch.complex128, device=dev) if out_device else np.zeros((len(chunks), nf, nt), dtype=complex)
     for g0 in range(0, len(chunks), per_group):
@@ -956,21 +1014,10 @@ def chunk_retrieval_batch(chunks, npad, tauMask, verbose=False, group_bytes=None
         # travel in ONE array each way; the padding value of a chunk (its mean, ththmod.py:783) is taken on the host.
         grids, etas, live, pads = [], [], [], []
         d_all = np.empty((len(group), nf, nt)) if dev_chunks is None else None
-        # (round 6) the chunks of one frequency row share their axes and edges: one _Grid per distinct (time step, frequency step,
-        # lengths, edges) instead of one per chunk -- 961 grid objects were 45 ms of a 0.23-s calc_wavefield, before any GPU work is
-        # queued.  The objects are read-only here (axes, centres, geometry).
-        grid_cache = {}
+        grid_cache = {}                  # (round 6) the chunks of one frequency row share one _Grid
         for k, (dspec2, edges, time, freq, eta) in enumerate(group):
             try:
-                time_v = np.asarray(units.strip(time, "time2", "s", warn=False))
-                freq_v = np.asarray(units.strip(freq, "freq2", "MHz", warn=False))
-                edges_v = np.asarray(units.strip(edges, "edges", "mHz", warn=False))
-                # (fft_axis reads only the length and the first step of an axis)
-                key = (time_v.shape[0], float(time_v[1] - time_v[0]), freq_v.shape[0], float(freq_v[1] - freq_v[0]), edges_v.tobytes())
-                grid = grid_cache.get(key)
-                if grid is None:
-                    grid = _Grid(fft_axis(freq_v, 1.0, npad), fft_axis(time_v, 1000.0, npad), edges_v)
-                    grid_cache[key] = grid
+                grid = _chunk_grid(time, freq, edges, npad, grid_cache)
                 e = np.array([_eta_float(eta)])
                 if (grid.geom.ntau, grid.geom.nfd) != (R, C) or (grids and grid.M != grids[0].M):
                     raise ValueError("axes or edges of this chunk do not match the chunk shape (%d, %d)" % (nf, nt))
@@ -995,14 +1042,7 @@ def chunk_retrieval_batch(chunks, npad, tauMask, verbose=False, group_bytes=None
             d_t = dev_chunks[g0:g0 + len(group)]
         else:
             d_t = dev_chunks[g0 + torch.as_tensor(np.asarray(live), device=dev)].contiguous()
-        lohi = np.zeros((len(live), 2), dtype=np.int64)
-        mask_us = float(units.strip(tauMask, "tauMask", "us", warn=False))
-        for j in range(len(live)):
-            sel = np.nonzero(np.abs(grids[j].tau) < mask_us)[0]
-            if sel.size:
-                lohi[j] = (int(sel[0]), int(sel[-1]) + 1)
-                if lohi[j, 1] - lohi[j, 0] != sel.size:
-                    raise ValueError("tau mask is not a contiguous block of delays")
+        lohi = _tau_mask_lohi(grids, tauMask)          # (outside the per-chunk try: a mask that is no block of delays ends the call)
         pads_a = np.ascontiguousarray(pads, dtype=np.float64)
         ws = workspace_for("scint_cs", nf, nt, npad)
         _lib.call("scint_cs_batch", d_t, len(live), nf, nt, npad, pads_a, lohi, 0, stack, ws, ws.numel(), stream_ptr())
@@ -1019,13 +1059,7 @@ def chunk_retrieval_batch(chunks, npad, tauMask, verbose=False, group_bytes=None
                 continue
             try:
                 rows_all[j, :n] = np.conjugate(V[j][:n]) * np.sqrt(float(w_list[j][0]))      # ththmod.py:1459-1461
-                tkey = (id(grids[j]), int(keeps[j][0]), n) if (n == int(keeps[j][-1]) - int(keeps[j][0]) + 1) else None
-                th_red = th_cache.get(tkey) if tkey is not None else None
-                if th_red is None:
-                    th_red = _theta_centres(grids[j].edges_red(keeps[j]))
-                    if tkey is not None:
-                        th_cache[tkey] = th_red
-                th_all[j, :n] = th_red
+                th_all[j, :n] = _reduced_centres_cached(grids[j], keeps[j], th_cache)
                 keep_n[j] = n
             except Exception as exc:
                 print("Chunk %d: %s" % (g0 + k, exc), flush=True)
@@ -1083,13 +1117,9 @@ def single_chunk_retrieval(params):
     reference.  Returns (model_E[nf, nt] complex, idx_f, idx_t); on failure a zero array, as
     the reference does.  The wavefield carries the arbitrary global phase of the eigenvector."""
     dspec2, edges, time, freq, eta, idx_t, idx_f, npad, tauMask, verbose = params
-    time_v = units.strip(time, "time2", "s", warn=False)
-    freq_v = units.strip(freq, "freq2", "MHz", warn=False)
+    _, _, edges_v, tau, fd = _chunk_axes(time, freq, edges, npad)      # (unit and axis errors propagate: outside the try)
     e = _eta_float(eta)
-    edges_v = units.strip(edges, "edges", "mHz", warn=False)
     dspec2 = np.asarray(dspec2, dtype=float)
-    fd = fft_axis(time_v, 1000.0, npad)
-    tau = fft_axis(freq_v, 1.0, npad)
     try:
         cs_t = conjugate_spectrum(dspec2, npad, tau, tauMask, True)
         grid = _Grid(tau, fd, edges_v)
@@ -1207,14 +1237,7 @@ def vlbi_retrieval_batch(chunks, npad, n_dish, tauMask, verbose=False, group_byt
     # host preparation of every chunk (grids are shared between chunks with equal axes and edges, as in chunk_retrieval_batch)
     grid_cache, prep = {}, []
     for k, (dlist, edges, time, freq, eta) in enumerate(chunks):
-        time_v = np.asarray(units.strip(time, "time2", "s", warn=False))
-        freq_v = np.asarray(units.strip(freq, "freq2", "MHz", warn=False))
-        edges_v = np.asarray(units.strip(edges, "edges", "mHz", warn=False))
-        key = (time_v.shape[0], float(time_v[1] - time_v[0]), freq_v.shape[0], float(freq_v[1] - freq_v[0]), edges_v.tobytes())
-        grid = grid_cache.get(key)
-        if grid is None:
-            grid = _Grid(fft_axis(freq_v, 1.0, npad), fft_axis(time_v, 1000.0, npad), edges_v)
-            grid_cache[key] = grid
+        grid = _chunk_grid(time, freq, edges, npad, grid_cache)
         if (grid.geom.ntau, grid.geom.nfd) != (R, C) or (prep and grid.M != prep[0][0].M):
             raise ValueError("chunk %d: axes or edges do not match the chunk shape (%d, %d)" % (k, nf, nt))
         for x in dlist:
@@ -1232,7 +1255,7 @@ def vlbi_retrieval_batch(chunks, npad, n_dish, tauMask, verbose=False, group_byt
     nmax = max(p_[2].shape[0] for p_ in prep)
     S = n_dish * nmax
     per_chunk = 16 * (nspec * R * C + S * S + (min(max_iter, S) + 4) * S) + 16 * nspec * nf * nt
-    per_group = int(min(65535, max(1, (RETRIEVAL_GROUP_BYTES if group_bytes is None else group_bytes) // per_chunk)))
+    per_group = _group_size(per_chunk, group_bytes, cap=65535)
 
     for g0 in range(0, len(chunks), per_group):
         group = chunks[g0:g0 + per_group]
@@ -1252,13 +1275,7 @@ def vlbi_retrieval_batch(chunks, npad, n_dish, tauMask, verbose=False, group_byt
                 pads[j * n_dish + q] = float(a.mean())                            # ththmod.py:1303
             for q, i in enumerate(vis_idx):
                 v_all[j * nvis + q] = np.asarray(c[0][i])
-        lohi = np.zeros((n, 2), dtype=np.int64)
-        for j in range(n):
-            sel = np.nonzero(np.abs(grids[j].tau) < mask_us)[0]                   # ththmod.py:1308 / 1325
-            if sel.size:
-                lohi[j] = (int(sel[0]), int(sel[-1]) + 1)
-                if lohi[j, 1] - lohi[j, 0] != sel.size:
-                    raise ValueError("tau mask is not a contiguous block of delays")
+        lohi = _tau_mask_lohi(grids, mask_us)                                     # ththmod.py:1308 / 1325
         stack = torch.empty((n * nspec, R, C), dtype=torch.complex128, device=dev)   # slots: the dynamic spectra, then the visibilities
         ws = workspace_for("scint_cs", nf, nt, npad)
         d_t = _dv.to_device(d_all, torch.float64)
@@ -1300,13 +1317,7 @@ def vlbi_retrieval_batch(chunks, npad, n_dish, tauMask, verbose=False, group_byt
         th_cache = {}
         for j in range(n):
             N = int(keep_n[j])
-            keep = prep[g0 + j][2]
-            tkey = (id(grids[j]), int(keep[0]), N) if N == int(keep[-1]) - int(keep[0]) + 1 else None
-            th_red = th_cache.get(tkey) if tkey is not None else None
-            if th_red is None:
-                th_red = _theta_centres(grids[j].edges_red(keep))
-                if tkey is not None:
-                    th_cache[tkey] = th_red
+            th_red = _reduced_centres_cached(grids[j], prep[g0 + j][2], th_cache)
             with np.errstate(invalid="ignore"):
                 amp = np.sqrt(w[j])                                                # ththmod.py:1376
             for d in range(n_dish):
@@ -1776,12 +1787,8 @@ def calc_asymmetry(params):
     eigenvector of the reduced theta-theta is needed, so the model/back-map steps of the
     reference's modeler call are skipped.  Returns (asymm, idx_f, idx_t); NaN on failure."""
     dspec2, edges, time, freq, eta, idx_t, idx_f, npad, verbose = params
-    time_v = units.strip(time, "time2", "s", warn=False)
-    freq_v = units.strip(freq, "freq2", "MHz", warn=False)
+    _, _, edges_v, tau, fd = _chunk_axes(time, freq, edges, npad)
     e = _eta_float(eta)
-    edges_v = units.strip(edges, "edges", "mHz", warn=False)
-    fd = fft_axis(time_v, 1000.0, npad)
-    tau = fft_axis(freq_v, 1.0, npad)
     try:
         cs_t = conjugate_spectrum(np.asarray(dspec2, dtype=float), npad)
         w, V_t, info = eigvec_sweep(cs_t, tau, fd, np.array([e]), edges_v)
@@ -2022,12 +2029,8 @@ def single_search_thin(params):
     reference (padding with dspec2.mean(), no delay mask).  Plotting is not supported (`plot=True` only warns).  Returns
     (eta_fit, eta_sig, freq.mean(), time.mean(), eigs) with eigs the singular values of the curvatures that did not fail."""
     (dspec2, freq, time, etas, edges, name, plot, fw, npad, coher, verbose, edgesArclet, centerCut) = params
-    time_v = units.strip(time, "time", "s", warn=False)
-    freq_v = units.strip(freq, "freq", "MHz", warn=False)
+    time_v, freq_v, edges_v, tau, fd = _chunk_axes(time, freq, edges, npad, ("time", "freq"))      # ththmod.py:582-583
     etas_v = np.atleast_1d(units.strip(etas, "etas", "s3", warn=False)).astype(float)
-    edges_v = units.strip(edges, "edges", "mHz", warn=False)
-    fd = fft_axis(time_v, 1000.0, npad)          # ththmod.py:582
-    tau = fft_axis(freq_v, 1.0, npad)            # ththmod.py:583
     # coherent: CS; incoherent: |CS|^2 (ththmod.py:630-631) -- scint_cs's incoherent mode is |CS|, so square it here
     cs_t = conjugate_spectrum(dspec2, npad, coher=True)
     if not coher:

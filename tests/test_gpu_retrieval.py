@@ -121,6 +121,39 @@ def test_chunk_retrieval_batch_on_dense_grids_vs_oracle(thth, to, npad, nedge):
     assert np.abs(rc.align(got, ref) - ref).max() <= 1e-9 * np.abs(ref).max()
 
 
+def test_grouped_retrieval_with_a_failing_chunk_shares_grids(thth, capsys, monkeypatch):
+    """Four 16 x 12 chunks of one frequency row at npad = 1 in two groups of two.  Chunk 2 carries a single edge, a grid that
+    cannot be built: it is reported and left zero, and chunk 3 takes its slot of the second group's stack.  The other three
+    equal their own single_chunk_retrieval to 1e-9 of the peak after removing the global phase.  Grids are shared within a group:
+    three constructions -- one for chunks 0 and 1 together, the failing one of chunk 2, one for chunk 3."""
+    from scintools_amd.synth import arc_dynspec
+    npad = 1
+    time, freq, tau, fd, edges, eta = rc.geometry(16, 12, npad, 14, 1.0)
+    chunks = []
+    for k in range(4):
+        dyn = arc_dynspec(16, 12, seed=70 + k, nimg=6)[0]
+        chunks.append((dyn - dyn.mean(), edges.copy(), time.copy(), freq.copy(), eta))
+    chunks[2] = (chunks[2][0], edges[:1]) + chunks[2][2:]
+    built = []
+    init = thth._Grid.__init__
+
+    def counting(self, tau, fd, edges):
+        built.append(np.shape(edges)[0])
+        init(self, tau, fd, edges)
+    with monkeypatch.context() as m:
+        m.setattr(thth._Grid, "__init__", counting)
+        got = thth.chunk_retrieval_batch(chunks, npad, 0.0, group_bytes=2 * 16 * (2 * 16) * (2 * 12))
+    assert built == [14, 1, 14]          # (the count before the chunk preparation moved into ththmod._chunk_grid: the same three)
+    assert "Chunk 2: " in capsys.readouterr().out
+    assert got.shape == (4, 16, 12) and not got[2].any()
+    for k in (0, 1, 3):
+        ref = thth.single_chunk_retrieval(chunks[k] + (0, 0, npad, 0.0, False))[0]
+        assert np.abs(ref).max() > 0
+        err = np.abs(rc.align(got[k], ref) - ref).max() / np.abs(ref).max()
+        print(f"chunk {k}: batch against single_chunk_retrieval {err:.2e} of the peak")
+        assert err <= 1e-9, k
+
+
 def test_dense_grid_wavefield_batched_route_equals_pool_route(thth, golden):
     """A Dynspec of several chunks with a dense nedge (about 17 centres per Doppler bin at npad = 1): calc_wavefield (batched
     route, retrieval tail) against thetatheta_chunks(pool=...) (single_chunk_retrieval per chunk, the general back-map), each
