@@ -55,7 +55,8 @@ extern "C" {
  *   107: the rank-1 Hermitian back-map on a uniform theta grid is rev_diag_kernel (scint_rev_map leaves which kernel ran in word 9
  *        of its workspace; SCINT_REV_DIAG=0 keeps the general kernel);
  *   108: scint_two_curve_map / scint_sv_sweep_multi (the thin-screen search, scint_thin_geom);
- *   (the VLBI entry points -- scint_cs_complex_batch / scint_vlbi_composite / scint_eigh_top_batch -- only ADD symbols: no bump) */
+ *   (the VLBI entry points -- scint_cs_complex_batch / scint_vlbi_composite / scint_eigh_top_batch -- and the batched 1-D ACF fit --
+ *   scint_acf1d_fit -- only ADD symbols: no bump; a build without them fails at load, which checks every declared symbol) */
 #define SCINT_ABI_VERSION 108
 
 #define SCINT_OK 0
@@ -479,6 +480,33 @@ int32_t scint_acf_row_peaks(const double* acf, int64_t R, int64_t C, const int32
                             int32_t* col_out, double* win_out, int32_t* flag_out, void* stream);
 int32_t scint_segment_cut(const double* dyn, int64_t nf, int64_t nt, int64_t fnum, int64_t tnum, int64_t nfseg,
                           int64_t ntseg, double* segs_out, void* stream);
+
+/* ---- batched 1-D ACF fits of tau and dnu: Dynspec.get_scint_params(method='acf1d') of the reference, for a stack ----------
+ * Replaces, per problem b < B of acf[B][R][C] (as scint_acf writes an ACF), dynspec.py:2575-2608 (the two half-cuts
+ * acf[R/2:, C/2] and acf[R/2, C/2:], the start values wn, amp, tau, dnu and the crop to nscale scales or 5 samples), :2650-2687
+ * (the weights; `bartlett`: Brockwell & Davis 7.2.5 on the CROPPED cut) and :2698-2702 with scint_models.py:62-120: the
+ * least-squares fit of
+ *   r_t = (y_t - amp exp(-(x_t / tau)^alpha) (1 - x_t / max x_t)) w_t,  r_f = (y_f - amp exp(-x_f ln2 / dnu) (1 - x_f / max x_f)) w_f
+ * over (tau, dnu, amp), and alpha when alpha_varies (started at `alpha`), by Levenberg-Marquardt in (log tau, log dnu, log amp,
+ * alpha) -- the scales stay positive, as the reference's min=0 -- with an analytic Jacobian.  One wavefront per problem, at most
+ * max_iter (1 .. 100000) passes each: no problem can spin.  No atomics; equal inputs give equal bits, whatever the neighbours.
+ *   dt, df      sample steps of the two cuts; bw[B], tobs[B] (device): the fallbacks for dnu and tau without a crossing;
+ *   values_out [B][4]  tau, dnu, amp, alpha;  errors_out [B][4]: sqrt(diag((J^T J)^-1 chi^2 / (N - nvary))) in these external
+ *               parameters, N = all residuals (the two zero-weighted first samples included); alpha and 0 when alpha is fixed;
+ *   stats_out [B][2]   chi^2 = sum r^2 and chi^2 / (N - nvary);   niter_out[B] passes made;
+ *   status_out[B]      0 converged (the last step moved no scale by more than 1e-12 of itself, alpha by 1e-12), 1 max_iter reached,
+ *               2 singular normal matrix (or a start scale that is not positive), 3 non-finite sample in a half-cut,
+ *               4 non-finite cost or step.  Every status but 0 leaves NaN in values_out, errors_out and stats_out;
+ *   setup_out [B][6] or NULL: the start values wn, amp, tau, dnu and the crop lengths n_t, n_f (as doubles; NaN start values for
+ *               status 3).
+ * Workspace (scint_acf1d_fit_workspace_bytes), per problem 2 (n_tc + n_fc) doubles with n_tc = C - C/2, n_fc = R - R/2: the
+ * half-cuts y_t[n_tc], y_f[n_fc], then their weights w_t, w_f (n_t and n_f of them valid).  R, C >= 6.  Asynchronous. */
+int32_t scint_acf1d_fit_workspace_bytes(int64_t B, int64_t R, int64_t C, size_t* SCINT_HOST bytes);
+int32_t scint_acf1d_fit(const double* acf, int64_t B, int64_t R, int64_t C, double dt, double df, const double* bw,
+                        const double* tobs, double nscale, int32_t full_frame, int32_t weighted, int32_t bartlett,
+                        double alpha, int32_t alpha_varies, int32_t max_iter, double* values_out, double* errors_out,
+                        double* stats_out, int32_t* niter_out, int32_t* status_out, double* setup_out, void* workspace,
+                        size_t workspace_bytes, void* stream);
 
 /* ---- chi^2: sum((model[:nf,:nt]-dspec)[mask]**2)/N (ththmod.py:364-367) --- */
 /* mask: uint8[nf*nt] or NULL (= isfinite(dspec)).  out: DEVICE double[1].  Asynchronous. */

@@ -301,6 +301,8 @@ class Dynspec:
     get_scint_params = scintpar.get_scint_params
     get_acf_tilt = scintpar.get_acf_tilt
     cut_dyn = scintpar.cut_dyn
+    fit_scint_params = scintpar.fit_scint_params
+    fit_scint_params_cut = scintpar.fit_scint_params_cut
 
     @property
     def normsspec(self):

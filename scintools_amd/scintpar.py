@@ -14,8 +14,16 @@ The functions are bound onto ``scintools_amd.dynspec.Dynspec`` as ``arcfit``'s a
   ACF from device memory, each output stack downloaded once.  ``self.cutacf`` is the one addition: the reference computes every
   segment's ACF and discards it.
 
-The fitted methods (``acf1d``, ``acf2d_approx``, ``acf2d``, ``sspec``, ``mcmc``) need lmfit and raise ``NotImplementedError``.
+The fitted methods of ``get_scint_params`` (``acf1d``, ``acf2d_approx``, ``acf2d``, ``sspec``, ``mcmc``) need lmfit and raise
+``NotImplementedError``.  The 1-D ACF fit itself -- the reference's default, dynspec.py:2650-2702 with scint_models.py:62-120 -- runs
+on the device under names of its own:
+
+* ``acf1d_fit_device``: a stack of ACFs in HBM, one Levenberg-Marquardt problem per wavefront, one launch (``scint_acf1d_fit``).
+* ``fit_scint_params``: the batch of one on ``self.acf``; sets what the reference sets after an ``acf1d`` fit.
+* ``fit_scint_params_cut``: every segment of ``cut_dyn`` -- cut, ACF and fit on the device, one fit launch for all of them.
 """
+import warnings
+
 import numpy as np
 import torch
 
@@ -23,6 +31,11 @@ from . import _lib, device
 from .arcfit import fit_parabola
 
 PEAK_WINDOW = 7            # acf[row, x - 3 : x + 4] (csrc/scintpar.hpp, kPeakWindow)
+
+# status of a fit (csrc/scintpar.hpp, kFit*)
+FIT_CONVERGED, FIT_ITER_CAP, FIT_SINGULAR, FIT_NONFINITE_INPUT, FIT_NONFINITE_STEP = range(5)
+FIT_STATUS_TEXT = ("converged", "iteration cap reached", "singular normal matrix", "non-finite sample in a half-cut",
+                   "non-finite cost or step")
 
 _NEEDS_LMFIT = ("get_scint_params(method={0!r}) needs lmfit and is outside the accelerated path; "
                 "pass method='nofit' for the scales read off the ACF without a fit")
@@ -102,6 +115,45 @@ def segment_cut_device(dyn_t, fnum, tnum, nfseg, ntseg):
     nf, nt = (int(v) for v in dyn_t.shape)
     out = device.empty((nfseg * ntseg, fnum, tnum), torch.float64)
     _lib.call("scint_segment_cut", dyn_t, nf, nt, fnum, tnum, nfseg, ntseg, out, device.stream_ptr())
+    return out
+
+
+def acf1d_fit_device(acf_stack_t, dt, df, bw, tobs, alpha=5/3, nscale=5, full_frame=False, weighted=True, bartlett=True,
+                     max_iter=200, return_setup=False):
+    """Fit the 1-D ACF model to the central cuts of every ACF of a device stack [B, R, C] float64 (or one ACF [R, C]) in one launch
+    (``scint_acf1d_fit``; dynspec.py:2575-2608, 2650-2702, scint_models.py:62-120).  ``bw`` and ``tobs`` are scalars or one value per
+    problem (the fallbacks for ``dnu`` and ``tau`` without a crossing); ``alpha=None`` fits alpha, started at 5/3.  Returns a dict
+    of host arrays of length B: ``tau, dnu, amp, alpha`` and ``tauerr, dnuerr, amperr, alphaerr`` (the fit's standard errors: NaN
+    unless ``status == FIT_CONVERGED``), ``chisqr, redchi, niter, status`` and the start values ``tau0, dnu0, amp0, wn0`` with the
+    crop lengths ``n_t, n_f``.  ``return_setup`` adds ``y_t, y_f, w_t, w_f``: per problem the cropped cuts and their weights."""
+    _lib_ready()
+    if acf_stack_t.dim() == 2:
+        acf_stack_t = acf_stack_t[None]
+    if acf_stack_t.dim() != 3:
+        raise ValueError("acf1d_fit_device: expected a stack of ACFs [B, R, C]")
+    B, R, C = (int(v) for v in acf_stack_t.shape)
+    bw_t = device.to_device(np.array(np.broadcast_to(np.asarray(bw, dtype=np.float64), (B,))), torch.float64)
+    tobs_t = device.to_device(np.array(np.broadcast_to(np.asarray(tobs, dtype=np.float64), (B,))), torch.float64)
+    values, errors = device.empty((B, 4), torch.float64), device.empty((B, 4), torch.float64)
+    stats, setup = device.empty((B, 2), torch.float64), device.empty((B, 6), torch.float64)
+    niter, status = device.empty((B,), torch.int32), device.empty((B,), torch.int32)
+    ws = device.workspace_for("scint_acf1d_fit", B, R, C)
+    _lib.call("scint_acf1d_fit", acf_stack_t, B, R, C, float(dt), float(df), bw_t, tobs_t, float(nscale), 1 if full_frame else 0,
+              1 if weighted else 0, 1 if bartlett else 0, 5/3 if alpha is None else float(alpha), 1 if alpha is None else 0,
+              int(max_iter), values, errors, stats, niter, status, setup, ws, ws.numel(), device.stream_ptr())
+    values, errors, stats, setup = (t.cpu().numpy() for t in (values, errors, stats, setup))
+    out = dict(tau=values[:, 0], dnu=values[:, 1], amp=values[:, 2], alpha=values[:, 3], tauerr=errors[:, 0], dnuerr=errors[:, 1],
+               amperr=errors[:, 2], alphaerr=errors[:, 3], chisqr=stats[:, 0], redchi=stats[:, 1], niter=niter.cpu().numpy(),
+               status=status.cpu().numpy(), wn0=setup[:, 0], amp0=setup[:, 1], tau0=setup[:, 2], dnu0=setup[:, 3],
+               n_t=setup[:, 4].astype(np.int64), n_f=setup[:, 5].astype(np.int64))
+    if return_setup:
+        ntc, nfc = C - C // 2, R - R // 2
+        rows = ws[:16 * B * (ntc + nfc)].view(torch.float64).cpu().numpy().reshape(B, 2, ntc + nfc)
+        nt, nf = out["n_t"], out["n_f"]
+        out["y_t"] = [rows[b, 0, :nt[b]] for b in range(B)]
+        out["y_f"] = [rows[b, 0, ntc:ntc + nf[b]] for b in range(B)]
+        out["w_t"] = [rows[b, 1, :nt[b]] for b in range(B)]
+        out["w_f"] = [rows[b, 1, ntc:ntc + nf[b]] for b in range(B)]
     return out
 
 
@@ -313,3 +365,88 @@ def cut_dyn(self, tcuts=0, fcuts=0, plot=False, filename=None, dpi=200, lamsteps
     self.cutdyn = segs.cpu().numpy().reshape(fcuts + 1, tcuts + 1, fnum, tnum)
     self.cutsspec = sspecs.cpu().numpy().reshape(fcuts + 1, tcuts + 1, nrfft, ncfft)
     self.cutacf = acfs.cpu().numpy().reshape(fcuts + 1, tcuts + 1, 2 * fnum, 2 * tnum)
+
+
+def fit_scint_params(self, alpha=5/3, full_frame=False, nscale=5, weighted=True, bartlett=True, verbose=False):
+    """Scintillation timescale and bandwidth from the 1-D ACF fit, the reference's ``get_scint_params(method='acf1d')``
+    (dynspec.py:2650-2702, 2953-3002), on the device: the batch of one of ``acf1d_fit_device`` on ``self.acf``.  First the no-fit
+    values and by-products of ``get_scint_params(method='nofit')``; a converged fit then sets ``tau, dnu, tscat, nscint, fse_tau,
+    fse_dnu, tauerr, dnuerr`` (fit error and finite-scintle error in quadrature), ``amp, amperr, wn, talpha, talphaerr`` and
+    ``scint_param_method = 'acf1d'``.  ``alpha=None`` fits alpha.  Always sets ``scint_fit_status`` (``FIT_*``),
+    ``scint_fit_redchi`` and ``scint_fit_niter``; no ``report``.  A fit that did not converge warns and leaves the no-fit values."""
+    self.get_scint_params(method='nofit', full_frame=full_frame, nscale=nscale)
+    fit = acf1d_fit_device(type(self).acf.tensor(self), self.dt, self.df, self.bw, self.tobs, alpha=alpha, nscale=nscale,
+                           full_frame=full_frame, weighted=weighted, bartlett=bartlett)
+    self.scint_fit_status = int(fit["status"][0])
+    self.scint_fit_redchi = float(fit["redchi"][0])
+    self.scint_fit_niter = int(fit["niter"][0])
+    if self.scint_fit_status != FIT_CONVERGED:
+        warnings.warn(f"fit_scint_params: the fit did not converge ({FIT_STATUS_TEXT[self.scint_fit_status]} after "
+                      f"{self.scint_fit_niter} iterations); the no-fit values are kept")
+        return
+    self.scint_param_method = 'acf1d'
+    self.tau = float(fit["tau"][0])
+    self.dnu = float(fit["dnu"][0])
+    self.tscat = 1/(2*np.pi*self.dnu)  # scattering timescale
+    if self.dnu < self.df:
+        print("Warning: Scint bandwidth < channel bandwidth.")
+    # Compute finite scintle error
+    nscint = (1 + 0.2*self.bw/(self.dnu)) * \
+        (1 + 0.2*self.tobs/(self.tau*np.log(2)))
+    self.nscint = nscint
+    self.fse_tau = self.tau/(2*np.sqrt(nscint))
+    fit_tau = float(fit["tauerr"][0])
+    self.fse_dnu = self.dnu/(2*np.sqrt(nscint))
+    fit_dnu = float(fit["dnuerr"][0])
+    if verbose:
+        print("\nFinite scintle errors (tau, dnu):\n", self.fse_tau, self.fse_dnu)
+        print("\nFit errors (tau, dnu):\n", fit_tau, fit_dnu)
+    self.tauerr = np.sqrt(fit_tau**2 + self.fse_tau**2)
+    self.dnuerr = np.sqrt(fit_dnu**2 + self.fse_dnu**2)
+    self.amp = float(fit["amp"][0])
+    self.amperr = float(fit["amperr"][0])
+    self.wn = 1 - self.amp
+    if 'sim:mb2=' in self.name:
+        self.wn = 0
+    if alpha is None:
+        self.talpha = float(fit["alpha"][0])
+        self.talphaerr = float(fit["alphaerr"][0])
+    else:
+        self.talpha = alpha
+        self.talphaerr = 0
+    return
+
+
+def fit_scint_params_cut(self, tcuts=0, fcuts=0, alpha=5/3, full_frame=False, nscale=5, weighted=True, bartlett=True,
+                         verbose=False):
+    """The 1-D ACF fit of every segment of ``cut_dyn(tcuts, fcuts)``: the segments are cut on the device, every segment's ACF
+    (no mean subtracted, as ``cut_dyn``) goes into one stack ``[B, 2 fnum, 2 tnum]`` and ONE launch fits them all, each with its
+    own ``bw = fnum df`` and ``tobs = tnum dt``.  Sets ``cut_tau, cut_dnu, cut_tauerr, cut_dnuerr`` (the fit's standard errors),
+    ``cut_amp`` and ``cut_fit_status``, each ``[fcuts + 1, tcuts + 1]``; a segment whose fit did not converge holds NaN."""
+    _lib_ready()
+    nchan = len(self.freqs)  # re-define in case of trimming
+    nsub = len(self.times)
+    fnum = int(np.floor(nchan/(fcuts + 1)))
+    tnum = int(np.floor(nsub/(tcuts + 1)))
+    if fcuts < 0 or tcuts < 0 or fnum < 3 or tnum < 5:
+        raise ValueError(f"fit_scint_params_cut: segments of {fnum} channels x {tnum} sub-integrations are too small "
+                         "(at least 3 x 5)")
+    dyn = np.asarray(self.dyn, dtype=float)
+    if dyn.shape[0] < (fcuts + 1) * fnum or dyn.shape[1] < (tcuts + 1) * tnum:
+        raise ValueError("fit_scint_params_cut: dyn is smaller than its frequency and time axes")
+    if not np.all(np.isfinite(dyn[:(fcuts + 1) * fnum, :(tcuts + 1) * tnum])):
+        raise ValueError("fit_scint_params_cut on the GPU needs a finite dynamic spectrum (run refill first)")
+    nseg = (fcuts + 1) * (tcuts + 1)
+    segs = segment_cut_device(device.to_device(dyn, torch.float64), fnum, tnum, fcuts + 1, tcuts + 1)
+    acfs = device.empty((nseg, 2 * fnum, 2 * tnum), torch.float64)
+    for k in range(nseg):
+        acf_device(segs[k], subtract_mean=False, out=acfs[k])
+    fit = acf1d_fit_device(acfs, self.dt, self.df, fnum * self.df, tnum * self.dt, alpha=alpha, nscale=nscale,
+                           full_frame=full_frame, weighted=weighted, bartlett=bartlett)
+    shape = (fcuts + 1, tcuts + 1)
+    self.cut_tau, self.cut_dnu, self.cut_amp = (fit[k].reshape(shape) for k in ("tau", "dnu", "amp"))
+    self.cut_tauerr, self.cut_dnuerr = fit["tauerr"].reshape(shape), fit["dnuerr"].reshape(shape)
+    self.cut_fit_status = fit["status"].reshape(shape)
+    if verbose:
+        print(f"fit_scint_params_cut: {int((self.cut_fit_status == FIT_CONVERGED).sum())} of {nseg} fits converged")
+    return
