@@ -56,7 +56,7 @@ extern "C" {
  *        of its workspace; SCINT_REV_DIAG=0 keeps the general kernel);
  *   108: scint_two_curve_map / scint_sv_sweep_multi (the thin-screen search, scint_thin_geom);
  *   (the VLBI entry points -- scint_cs_complex_batch / scint_vlbi_composite / scint_eigh_top_batch -- and the batched 1-D ACF fit --
- *   scint_acf1d_fit -- only ADD symbols: no bump; a build without them fails at load, which checks every declared symbol) */
+ *   scint_acf1d_fit -- and the approximate 2-D one -- scint_acf2d_approx_fit -- only ADD symbols: no bump; a build without them fails at load, which checks every declared symbol) */
 #define SCINT_ABI_VERSION 108
 
 #define SCINT_OK 0
@@ -507,6 +507,41 @@ int32_t scint_acf1d_fit(const double* acf, int64_t B, int64_t R, int64_t C, doub
                         double alpha, int32_t alpha_varies, int32_t max_iter, double* values_out, double* errors_out,
                         double* stats_out, int32_t* niter_out, int32_t* status_out, double* setup_out, void* workspace,
                         size_t workspace_bytes, void* stream);
+
+/* ---- batched approximate 2-D ACF fits of tau, dnu and the phase gradient: get_scint_params(method='acf2d_approx') ---------
+ * (dynspec.py:2710-2842 with scint_models.py:123-161; csrc/acf2d.hpp).  The host chooses per problem b < B of acf[B][R][C] a
+ * window rect[b] = (f0, nfw, t0, ntw) (rows f0 .. f0 + nfw, columns t0 .. t0 + ntw; device int32) centred on the ACF's maximum
+ * and the start values start[b] = (tau, dnu, amp, alpha, phasegrad); the fit minimises the sum of squares of
+ *   r = (y - amp exp(-(|(t - 60 phasegrad f) / tau|^(3 alpha / 2) + |f ln2 / dnu|^(3/2))^(2/3)) (1 - |t| / tobs) (1 - |f| / bw)) w
+ * over the window, t and f the ticks of np.linspace(-tobs, tobs, C + 1)[:-1] and np.linspace(-bw, bw, R + 1)[:-1], by
+ * Levenberg-Marquardt in (log tau, log dnu, log amp, phasegrad, alpha) with an analytic Jacobian; tau leaves the problem when
+ * !tau_varies, alpha when !alpha_varies.  The weights are computed in the kernel: W0 = sqrt(nsub nchan (T / max tticks)
+ * (F / max fticks)) with T = tobs - |t|, F = bw - |f| (1 when !weighted), zero where not finite or where y - 1 / W0 < 0, rolled by
+ * -1 in both axes (the reference's double fftshift on an odd window), zero at the window's centre.  One 256-thread workgroup per
+ * problem, one launch, at most max_iter (1 .. 100000) passes each; no atomics, equal inputs give equal bits.
+ *   scint_acf_argmax   idx_out[b] (device int32) = np.argmax(acf[b]): ties resolve to the lowest flat index, NaN is never the
+ *               maximum.  R C < 2^31.
+ *   status_in[B]       device int32; non-zero: the host gave up on the problem (its status is passed on, NaN outputs);
+ *   values_out [B][5]  tau, dnu, amp, alpha, phasegrad;  errors_out [B][5]: sqrt(diag((J^T J)^-1 chi^2 / (N - nvary))) in these
+ *               external parameters, N = nfw ntw (zero-weight points included), 0 for a parameter that does not vary;
+ *   stats_out [B][2]   chi^2 and chi^2 / (N - nvary);  niter_out[B] passes made;  nnz_out[B] number of non-zero weights;
+ *   status_out[B]      0 .. 4 as scint_acf1d_fit (3: passed on from status_in), 5 the rectangle has an even or empty side or
+ *               leaves the ACF (nothing outside acf[b] is ever read).  Every status but 0 leaves NaN in values, errors, stats.
+ * Workspace (scint_acf2d_approx_fit_workspace_bytes): 256 bytes, and with return_setup per problem 2 R C doubles: the window's y,
+ * row-major in the first nfw ntw, then from R C on its weights.  R, C >= 6, R C < 2^31.  Asynchronous.
+ * scint_acf2d_approx_model: out[nf][nt] = (ydata - model(tdata[j], fdata[i])) weights, ydata NULL = 0, weights NULL = 1, the
+ *   weight at ((nf - 1) / 2, (nt - 1) / 2) zero (scint_models.py:156-158): scint_acf_model_2d_approx for device arrays. */
+int32_t scint_acf_argmax(const double* acf, int64_t B, int64_t R, int64_t C, int32_t* idx_out, void* stream);
+int32_t scint_acf2d_approx_fit_workspace_bytes(int64_t B, int64_t R, int64_t C, int32_t return_setup, size_t* SCINT_HOST bytes);
+int32_t scint_acf2d_approx_fit(const double* acf, int64_t B, int64_t R, int64_t C, const int32_t* rect, const double* start,
+                               const int32_t* status_in, const double* bw, const double* tobs, double nsub, double nchan,
+                               int32_t weighted, int32_t tau_varies, int32_t alpha_varies, int32_t max_iter,
+                               double* values_out, double* errors_out, double* stats_out, int32_t* niter_out,
+                               int32_t* status_out, int32_t* nnz_out, int32_t return_setup, void* workspace,
+                               size_t workspace_bytes, void* stream);
+int32_t scint_acf2d_approx_model(const double* tdata, int64_t nt, const double* fdata, int64_t nf, const double* ydata,
+                                 const double* weights, double tau, double dnu, double amp, double alpha, double phasegrad,
+                                 double tobs, double bw, double* out, void* stream);
 
 /* ---- chi^2: sum((model[:nf,:nt]-dspec)[mask]**2)/N (ththmod.py:364-367) --- */
 /* mask: uint8[nf*nt] or NULL (= isfinite(dspec)).  out: DEVICE double[1].  Asynchronous. */

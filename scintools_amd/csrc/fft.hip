@@ -1462,6 +1462,7 @@ extern "C" int32_t scint_divide_by_max(double* x, int64_t n, void* workspace, si
 }
 
 #include "scintpar.hpp"
+#include "acf2d.hpp"
 
 // ------------------------------------------------------------------------------
 // scint_chisq_sweep: chisq_calc(modeler(...)) for every curvature in ONE call

@@ -129,6 +129,7 @@ class Dynspec:
     vsspec = DeviceBacked("vsspec")
     vlamsspec = DeviceBacked("vlamsspec")
     trapsspec = DeviceBacked("trapsspec")
+    acf_model = DeviceBacked("acf_model")    # the fitted approximate 2-D model over the fit's window (fit_scint_params_2d)
     acf =DeviceBacked("acf")                # [2 nf, 2 nt]: 512 MB for a 4096^2 observation; the scales read a few cuts of it
 
     def __init__(self, filename=None, dyn=None, verbose=True, process=False, lamsteps=False,
@@ -303,6 +304,8 @@ class Dynspec:
     cut_dyn = scintpar.cut_dyn
     fit_scint_params = scintpar.fit_scint_params
     fit_scint_params_cut = scintpar.fit_scint_params_cut
+    fit_scint_params_2d = scintpar.fit_scint_params_2d
+    fit_scint_params_2d_cut = scintpar.fit_scint_params_2d_cut
 
     @property
     def normsspec(self):

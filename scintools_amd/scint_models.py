@@ -51,6 +51,17 @@ def scint_acf_model_2d(params, ydata, weights):
     return (ydata - model) * weights
 
 
+def scint_acf_model_2d_approx(params, tdata, fdata, ydata, weights):
+    """Fit an approximate 2D ACF function (scint_models.py:123-161): ``(ydata - model) * weights`` [nf, nt] with the weight of the
+    white-noise pixel zeroed, evaluated on the device (``scint_acf2d_approx_model``) and returned as a host array.  ``params``
+    holds ``amp, dnu, tau, alpha, phasegrad`` (min/MHz), ``tobs, bw``."""
+    from . import scintpar
+    parvals = params.valuesdict() if hasattr(params, "valuesdict") else params
+    out = scintpar.acf2d_approx_model_device(tdata, fdata, ydata, weights, parvals['tau'], parvals['dnu'], parvals['amp'],
+                                             parvals['alpha'], parvals['phasegrad'], parvals['tobs'], parvals['bw'])
+    return out.cpu().numpy()
+
+
 def effective_velocity_annual(params, true_anomaly, vearth_ra, vearth_dec, mjd=None):
     """Effective velocity with the annual and the pulsar's orbital and proper-motion terms, in RA and DEC, km/s
     (scint_models.py:504-587).  The ISM velocity is NOT included; the result is in the ISM's frame.  `params` is a dictionary

@@ -21,6 +21,10 @@ on the device under names of its own:
 * ``acf1d_fit_device``: a stack of ACFs in HBM, one Levenberg-Marquardt problem per wavefront, one launch (``scint_acf1d_fit``).
 * ``fit_scint_params``: the batch of one on ``self.acf``; sets what the reference sets after an ``acf1d`` fit.
 * ``fit_scint_params_cut``: every segment of ``cut_dyn`` -- cut, ACF and fit on the device, one fit launch for all of them.
+
+So does the approximate 2-D fit (``method='acf2d_approx'``, dynspec.py:2689-2842 with scint_models.py:123-161), the one that yields
+the phase gradient: ``acf2d_approx_fit_device`` (one workgroup per problem, ``scint_acf2d_approx_fit``, csrc/acf2d.hpp),
+``fit_scint_params_2d`` and ``fit_scint_params_2d_cut``.
 """
 import warnings
 
@@ -34,8 +38,9 @@ PEAK_WINDOW = 7            # acf[row, x - 3 : x + 4] (csrc/scintpar.hpp, kPeakWi
 
 # status of a fit (csrc/scintpar.hpp, kFit*)
 FIT_CONVERGED, FIT_ITER_CAP, FIT_SINGULAR, FIT_NONFINITE_INPUT, FIT_NONFINITE_STEP = range(5)
+FIT_BAD_WINDOW = 5         # the 2-D fit only (csrc/acf2d.hpp, kFitBadWindow)
 FIT_STATUS_TEXT = ("converged", "iteration cap reached", "singular normal matrix", "non-finite sample in a half-cut",
-                   "non-finite cost or step")
+                   "non-finite cost or step", "the fit window has an even or empty side")
 
 _NEEDS_LMFIT = ("get_scint_params(method={0!r}) needs lmfit and is outside the accelerated path; "
                 "pass method='nofit' for the scales read off the ACF without a fit")
@@ -449,4 +454,273 @@ def fit_scint_params_cut(self, tcuts=0, fcuts=0, alpha=5/3, full_frame=False, ns
     self.cut_fit_status = fit["status"].reshape(shape)
     if verbose:
         print(f"fit_scint_params_cut: {int((self.cut_fit_status == FIT_CONVERGED).sum())} of {nseg} fits converged")
+    return
+
+
+# ----------------------------------------------------------------------------
+# the approximate 2-D ACF fit: tau, dnu and the phase gradient (csrc/acf2d.hpp)
+# ----------------------------------------------------------------------------
+def acf_argmax_device(acf_stack_t):
+    """``np.argmax`` of every ACF of a device stack [B, R, C] (first occurrence; NaN is never the maximum) as a host array."""
+    _lib_ready()
+    B, R, C = (int(v) for v in acf_stack_t.shape)
+    idx = device.empty((B,), torch.int32)
+    _lib.call("scint_acf_argmax", acf_stack_t, B, R, C, idx, device.stream_ptr())
+    return idx.cpu().numpy().astype(np.int64)
+
+
+def acf2d_window(nf, nt, loc, tau, dnu, dt, df, bw, tobs, nscale=5, full_frame=False):
+    """The window of the 2-D fit as a rectangle ``(f0, nfw, t0, ntw)`` of ACF indices: dynspec.py:2733-2783 statement for
+    statement, on index ranges instead of arrays (a ``range`` slices with NumPy's clipping).  ``loc`` is the flat index of the
+    ACF's maximum, ``tau`` and ``dnu`` are the NO-FIT scales: the reference's locals are not updated by the 1-D fit.  Its
+    frequency branch sets ``tmin = 0; tmax = nf`` and leaves ``fmin, fmax`` as they were; so does this."""
+    tau, dnu = np.float64(tau), np.float64(dnu)
+    wn_loc = divmod(int(loc), nt)
+
+    fleft = wn_loc[0]
+    fright = nf - wn_loc[0] - 1
+    fmin = wn_loc[0] - min(fleft, fright)
+    fmax = wn_loc[0] + min(fleft, fright) + 1
+
+    tleft = wn_loc[1]
+    tright = nt - wn_loc[1] - 1
+    tmin = wn_loc[1] - min(tleft, tright)
+    tmax = wn_loc[1] + min(tleft, tright) + 1
+
+    rows = range(nf)[fmin:fmax]
+    cols = range(nt)[tmin:tmax]
+
+    if nscale is not None and not full_frame:
+        ntau = nscale
+        ndnu = nscale
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if ntau > (tobs / tau):
+                tmin = 0
+                tmax = nt
+            else:
+                tframe = int(round(ntau * (tau / dt)))
+                tmin = int(np.floor(len(cols) / 2)) - tframe
+                tmax = int(np.floor(len(cols) / 2)) + tframe + 1
+
+            if ndnu > (bw / dnu):
+                tmin = 0
+                tmax = nf
+            else:
+                fframe = int(round(ndnu * (dnu / df)))
+                fmin = int(np.floor(len(rows) / 2)) - fframe
+                fmax = int(np.floor(len(rows) / 2)) + fframe + 1
+        rows = rows[fmin:fmax]
+        cols = cols[tmin:tmax]
+    return (rows[0] if len(rows) else 0, len(rows), cols[0] if len(cols) else 0, len(cols))
+
+
+def acf2d_approx_fit_device(acf_stack_t, dt, df, bw, tobs, nsub=None, nchan=None, alpha=5/3, nscale=5, full_frame=False,
+                            weighted=True, bartlett=True, phasegrad0=0.0, tau_vary_2d=True, tau_input=None, max_iter=200,
+                            return_setup=False):
+    """Fit the approximate 2-D ACF model (scint_models.py:123-161) to a window of every ACF of a device stack [B, R, C] float64 (or
+    one ACF [R, C]): the reference's ``get_scint_params(method='acf2d_approx')`` (dynspec.py:2689-2842) for a batch.  Three
+    launches: the 1-D fit (``acf1d_fit_device``, unchanged) for the start values -- its ``tau, dnu, amp`` where it converged, the
+    no-fit values otherwise --, the ACFs' maxima (``scint_acf_argmax``), and the 2-D fit (``scint_acf2d_approx_fit``), one workgroup
+    per problem.  The windows are computed here, on the host, from the NO-FIT scales (``acf2d_window``); the weights in the kernel.
+    ``nsub``, ``nchan`` default to ``C // 2`` and ``R // 2``; ``alpha=None`` fits alpha from 5/3; ``phasegrad0`` and ``tau_input``
+    are scalars or one value per problem; ``tau_vary_2d=False`` keeps tau at its start value.  Returns a dict of host arrays of
+    length B: ``tau, dnu, amp, alpha, phasegrad``, their standard errors ``tauerr, ... phasegraderr`` (0 for a parameter that does
+    not vary; everything NaN unless ``status == FIT_CONVERGED``), ``chisqr, redchi, niter, status``, the rectangle ``f0, nfw, t0,
+    ntw``, ``nnz`` (non-zero weights), the start values ``tau_start, dnu_start, amp_start, alpha_start, phasegrad_start``, the
+    maxima ``argmax`` and ``fit1d``, the 1-D fit's own dict.  ``return_setup`` adds ``y`` and ``w``: per problem the window's samples
+    and weights [nfw, ntw].  ``FIT_BAD_WINDOW``: the reference's window has an even (or empty) side and is not centred."""
+    _lib_ready()
+    if acf_stack_t.dim() == 2:
+        acf_stack_t = acf_stack_t[None]
+    if acf_stack_t.dim() != 3:
+        raise ValueError("acf2d_approx_fit_device: expected a stack of ACFs [B, R, C]")
+    B, R, C = (int(v) for v in acf_stack_t.shape)
+    ws = device.workspace_for("scint_acf2d_approx_fit", B, R, C, 1 if return_setup else 0)   # (checks the shape first)
+    one = acf1d_fit_device(acf_stack_t, dt, df, bw, tobs, alpha=alpha, nscale=nscale, full_frame=full_frame, weighted=weighted,
+                           bartlett=bartlett, max_iter=max_iter)
+    bw_h = np.array(np.broadcast_to(np.asarray(bw, dtype=np.float64), (B,)))
+    tobs_h = np.array(np.broadcast_to(np.asarray(tobs, dtype=np.float64), (B,)))
+    locs = acf_argmax_device(acf_stack_t)
+
+    ok1 = one["status"] == FIT_CONVERGED
+    start = np.empty((B, 5))
+    start[:, 0] = np.where(ok1, one["tau"], one["tau0"])
+    start[:, 1] = np.where(ok1, one["dnu"], one["dnu0"])
+    start[:, 2] = np.where(ok1, one["amp"], one["amp0"])
+    start[:, 3] = 5/3 if alpha is None else float(alpha)
+    start[:, 4] = np.broadcast_to(np.asarray(phasegrad0, dtype=np.float64), (B,))
+    if tau_input is not None:
+        start[:, 0] = np.broadcast_to(np.asarray(tau_input, dtype=np.float64), (B,))
+    status_in = np.zeros(B, dtype=np.int32)
+    rect = np.zeros((B, 4), dtype=np.int32)
+    for b in range(B):
+        if not (np.isfinite(one["tau0"][b]) and np.isfinite(one["dnu0"][b]) and np.all(np.isfinite(start[b]))):
+            status_in[b] = FIT_NONFINITE_INPUT
+            continue
+        rect[b] = acf2d_window(R, C, locs[b], one["tau0"][b], one["dnu0"][b], dt, df, bw_h[b], tobs_h[b], nscale=nscale,
+                               full_frame=full_frame)
+
+    values, errors = device.empty((B, 5), torch.float64), device.empty((B, 5), torch.float64)
+    stats = device.empty((B, 2), torch.float64)
+    niter, status, nnz = (device.empty((B,), torch.int32) for _ in range(3))
+    _lib.call("scint_acf2d_approx_fit", acf_stack_t, B, R, C, device.to_device(rect, torch.int32),
+              device.to_device(start, torch.float64), device.to_device(status_in, torch.int32),
+              device.to_device(bw_h, torch.float64), device.to_device(tobs_h, torch.float64),
+              float(C // 2 if nsub is None else nsub), float(R // 2 if nchan is None else nchan), 1 if weighted else 0,
+              1 if tau_vary_2d else 0, 1 if alpha is None else 0, int(max_iter), values, errors, stats, niter, status, nnz,
+              1 if return_setup else 0, ws, ws.numel(), device.stream_ptr())
+    values, errors, stats = (t.cpu().numpy() for t in (values, errors, stats))
+    names = ("tau", "dnu", "amp", "alpha", "phasegrad")
+    out = {k: values[:, i] for i, k in enumerate(names)}
+    out.update({k + "err": errors[:, i] for i, k in enumerate(names)})
+    out.update({k + "_start": start[:, i] for i, k in enumerate(names)})
+    out.update(chisqr=stats[:, 0], redchi=stats[:, 1], niter=niter.cpu().numpy(), status=status.cpu().numpy(),
+               nnz=nnz.cpu().numpy().astype(np.int64), argmax=locs, fit1d=one)
+    out.update({k: rect[:, i].astype(np.int64) for i, k in enumerate(("f0", "nfw", "t0", "ntw"))})
+    if return_setup:
+        rows = np.array(ws[:16 * B * R * C].view(torch.float64).cpu().numpy()).reshape(B, 2, R * C)   # (the workspace is reused)
+        good = [b for b in range(B) if out["status"][b] not in (FIT_BAD_WINDOW, FIT_NONFINITE_INPUT)]
+        shape = {b: (int(rect[b, 1]), int(rect[b, 3])) for b in good}
+        out["y"] = [rows[b, 0, :shape[b][0] * shape[b][1]].reshape(shape[b]) if b in shape else None for b in range(B)]
+        out["w"] = [rows[b, 1, :shape[b][0] * shape[b][1]].reshape(shape[b]) if b in shape else None for b in range(B)]
+    return out
+
+
+def acf2d_approx_model_device(tdata, fdata, ydata, weights, tau, dnu, amp, alpha, phasegrad, tobs, bw):
+    """``(ydata - model) * weights`` of ``scint_acf_model_2d_approx`` as a device tensor [nf, nt] (``scint_acf2d_approx_model``);
+    ``ydata`` None: zeros, ``weights`` None: ones; host arrays are uploaded, device tensors are taken as they are."""
+    _lib_ready()
+    t = device.to_device(np.asarray(tdata, dtype=np.float64).reshape(-1), torch.float64) if not torch.is_tensor(tdata) else tdata
+    f = device.to_device(np.asarray(fdata, dtype=np.float64).reshape(-1), torch.float64) if not torch.is_tensor(fdata) else fdata
+    nt, nf = int(t.numel()), int(f.numel())
+
+    def grid(a, what):
+        if a is None or torch.is_tensor(a):
+            a_t = a
+        else:
+            a_t = device.to_device(np.asarray(a, dtype=np.float64), torch.float64)
+        if a_t is not None and tuple(a_t.shape) != (nf, nt):
+            raise ValueError(f"scint_acf_model_2d_approx: {what} has shape {tuple(a_t.shape)}, expected ({nf}, {nt})")
+        return a_t
+    out = device.empty((nf, nt), torch.float64)
+    _lib.call("scint_acf2d_approx_model", t, nt, f, nf, grid(ydata, "ydata"), grid(weights, "weights"), float(tau), float(dnu),
+              float(amp), float(alpha), float(phasegrad), float(tobs), float(bw), out, device.stream_ptr())
+    return out
+
+
+def _set_fit_results(self, fit, alpha, method, verbose):
+    """What the reference sets after a fit (dynspec.py:2953-3002) from problem 0 of a fit's dict."""
+    self.scint_param_method = method
+    self.tau = float(fit["tau"][0])
+    self.dnu = float(fit["dnu"][0])
+    self.tscat = 1/(2*np.pi*self.dnu)  # scattering timescale
+    if self.dnu < self.df:
+        print("Warning: Scint bandwidth < channel bandwidth.")
+    # Compute finite scintle error
+    nscint = (1 + 0.2*self.bw/(self.dnu)) * \
+        (1 + 0.2*self.tobs/(self.tau*np.log(2)))
+    self.nscint = nscint
+    self.fse_tau = self.tau/(2*np.sqrt(nscint))
+    fit_tau = float(fit["tauerr"][0])
+    self.fse_dnu = self.dnu/(2*np.sqrt(nscint))
+    fit_dnu = float(fit["dnuerr"][0])
+    if verbose:
+        print("\nFinite scintle errors (tau, dnu):\n", self.fse_tau, self.fse_dnu)
+        print("\nFit errors (tau, dnu):\n", fit_tau, fit_dnu)
+    self.tauerr = np.sqrt(fit_tau**2 + self.fse_tau**2)
+    self.dnuerr = np.sqrt(fit_dnu**2 + self.fse_dnu**2)
+    self.amp = float(fit["amp"][0])
+    self.amperr = float(fit["amperr"][0])
+    self.wn = 1 - self.amp
+    if 'sim:mb2=' in self.name:
+        self.wn = 0
+    if alpha is None:
+        self.talpha = float(fit["alpha"][0])
+        self.talphaerr = float(fit["alphaerr"][0])
+    else:
+        self.talpha = alpha
+        self.talphaerr = 0
+
+
+def fit_scint_params_2d(self, alpha=5/3, full_frame=False, nscale=5, weighted=True, bartlett=True, tau_vary_2d=True,
+                        tau_input=None, verbose=False):
+    """Scintillation timescale, bandwidth and phase gradient from the approximate 2-D ACF fit, the reference's
+    ``get_scint_params(method='acf2d_approx')`` (dynspec.py:2689-2842, 2953-3021), on the device: the batch of one of
+    ``acf2d_approx_fit_device`` on ``self.acf``.  First the no-fit values and by-products of ``get_scint_params(method='nofit')``,
+    then the 1-D fit for the start values; the phase gradient starts at ``acf_tilt`` when ``get_acf_tilt`` has set it with an
+    error, at 0 otherwise.  A converged fit sets everything ``fit_scint_params`` sets, ``scint_param_method = 'acf2d_approx'``, and
+    ``phasegrad`` (min/MHz), ``phasegraderr`` (the fit's standard error), ``fse_phasegrad`` and ``acf_model``: the model over the
+    fit's window, left on the device until it is read.  Always sets ``scint_fit_status`` (``FIT_*``), ``scint_fit_redchi`` and
+    ``scint_fit_niter``; no ``report``.  A fit that did not converge warns and keeps the 1-D fit's values where that converged
+    (``scint_param_method = 'acf1d'``), the no-fit values otherwise."""
+    self.get_scint_params(method='nofit', full_frame=full_frame, nscale=nscale)
+    phasegrad0 = 0.0
+    if hasattr(self, 'acf_tilt'):  # if have a confident measurement
+        if self.acf_tilt_err is not None:
+            phasegrad0 = self.acf_tilt
+    cls = type(self)
+    fit = acf2d_approx_fit_device(cls.acf.tensor(self), self.dt, self.df, self.bw, self.tobs, nsub=self.nsub, nchan=self.nchan,
+                                  alpha=alpha, nscale=nscale, full_frame=full_frame, weighted=weighted, bartlett=bartlett,
+                                  phasegrad0=phasegrad0, tau_vary_2d=tau_vary_2d, tau_input=tau_input)
+    self.scint_fit_status = int(fit["status"][0])
+    self.scint_fit_redchi = float(fit["redchi"][0])
+    self.scint_fit_niter = int(fit["niter"][0])
+    if self.scint_fit_status != FIT_CONVERGED:
+        one = fit["fit1d"]
+        kept = "1-D fit's" if one["status"][0] == FIT_CONVERGED else "no-fit"
+        warnings.warn(f"fit_scint_params_2d: the fit did not converge ({FIT_STATUS_TEXT[self.scint_fit_status]} after "
+                      f"{self.scint_fit_niter} iterations); the {kept} values are kept")
+        if one["status"][0] == FIT_CONVERGED:
+            _set_fit_results(self, one, alpha, 'acf1d', verbose)
+        return
+    _set_fit_results(self, fit, alpha, 'acf2d_approx', verbose)
+    f0, nfw, t0, ntw = (int(fit[k][0]) for k in ("f0", "nfw", "t0", "ntw"))
+    nr, nc = cls.acf.shape(self)
+    tdata = np.linspace(-self.tobs, self.tobs, nc + 1)[:-1][t0:t0 + ntw]
+    fdata = np.linspace(-self.bw, self.bw, nr + 1)[:-1][f0:f0 + nfw]
+    model = acf2d_approx_model_device(tdata, fdata, None, None, self.tau, self.dnu, self.amp, float(fit["alpha"][0]),
+                                      float(fit["phasegrad"][0]), self.tobs, self.bw)
+    cls.acf_model.park(self, model.neg_())          # (the reference negates the residual of a zero ACF)
+    self.phasegrad = float(fit["phasegrad"][0])
+    fse_ph = self.phasegrad * np.sqrt((self.fse_dnu/self.dnu)**2 +
+                                      (self.fse_tau/self.tau)**2)
+    self.phasegraderr = float(fit["phasegraderr"][0])
+    self.fse_phasegrad = fse_ph
+    return
+
+
+def fit_scint_params_2d_cut(self, tcuts=0, fcuts=0, alpha=5/3, full_frame=False, nscale=5, weighted=True, bartlett=True,
+                            tau_vary_2d=True, verbose=False):
+    """The approximate 2-D ACF fit of every segment of ``cut_dyn(tcuts, fcuts)``: cut, ACFs and fits on the device, ONE 1-D launch
+    and ONE 2-D launch for all segments, each with its own ``bw = fnum df``, ``tobs = tnum dt``, ``nchan = fnum``, ``nsub = tnum``.
+    Sets ``cut_tau, cut_dnu, cut_amp, cut_phasegrad``, their standard errors ``cut_tauerr, cut_dnuerr, cut_amperr,
+    cut_phasegraderr`` and ``cut_fit_status``, each ``[fcuts + 1, tcuts + 1]``; a segment whose fit did not converge holds NaN."""
+    _lib_ready()
+    nchan = len(self.freqs)  # re-define in case of trimming
+    nsub = len(self.times)
+    fnum = int(np.floor(nchan/(fcuts + 1)))
+    tnum = int(np.floor(nsub/(tcuts + 1)))
+    if fcuts < 0 or tcuts < 0 or fnum < 3 or tnum < 5:
+        raise ValueError(f"fit_scint_params_2d_cut: segments of {fnum} channels x {tnum} sub-integrations are too small "
+                         "(at least 3 x 5)")
+    dyn = np.asarray(self.dyn, dtype=float)
+    if dyn.shape[0] < (fcuts + 1) * fnum or dyn.shape[1] < (tcuts + 1) * tnum:
+        raise ValueError("fit_scint_params_2d_cut: dyn is smaller than its frequency and time axes")
+    if not np.all(np.isfinite(dyn[:(fcuts + 1) * fnum, :(tcuts + 1) * tnum])):
+        raise ValueError("fit_scint_params_2d_cut on the GPU needs a finite dynamic spectrum (run refill first)")
+    nseg = (fcuts + 1) * (tcuts + 1)
+    segs = segment_cut_device(device.to_device(dyn, torch.float64), fnum, tnum, fcuts + 1, tcuts + 1)
+    acfs = device.empty((nseg, 2 * fnum, 2 * tnum), torch.float64)
+    for k in range(nseg):
+        acf_device(segs[k], subtract_mean=False, out=acfs[k])
+    fit = acf2d_approx_fit_device(acfs, self.dt, self.df, fnum * self.df, tnum * self.dt, nsub=tnum, nchan=fnum, alpha=alpha,
+                                  nscale=nscale, full_frame=full_frame, weighted=weighted, bartlett=bartlett,
+                                  tau_vary_2d=tau_vary_2d)
+    shape = (fcuts + 1, tcuts + 1)
+    for k in ("tau", "dnu", "amp", "phasegrad"):
+        setattr(self, "cut_" + k, fit[k].reshape(shape))
+        setattr(self, "cut_" + k + "err", fit[k + "err"].reshape(shape))
+    self.cut_fit_status = fit["status"].reshape(shape)
+    if verbose:
+        print(f"fit_scint_params_2d_cut: {int((self.cut_fit_status == FIT_CONVERGED).sum())} of {nseg} fits converged")
     return
