@@ -56,7 +56,8 @@ extern "C" {
  *        of its workspace; SCINT_REV_DIAG=0 keeps the general kernel);
  *   108: scint_two_curve_map / scint_sv_sweep_multi (the thin-screen search, scint_thin_geom);
  *   (the VLBI entry points -- scint_cs_complex_batch / scint_vlbi_composite / scint_eigh_top_batch -- and the batched 1-D ACF fit --
- *   scint_acf1d_fit -- and the approximate 2-D one -- scint_acf2d_approx_fit -- only ADD symbols: no bump; a build without them fails at load, which checks every declared symbol) */
+ *   scint_acf1d_fit -- and the approximate 2-D one -- scint_acf2d_approx_fit -- and the biharmonic fill -- scint_inpaint_biharmonic --
+ *   only ADD symbols: no bump; a build without them fails at load, which checks every declared symbol) */
 #define SCINT_ABI_VERSION 108
 
 #define SCINT_OK 0
@@ -818,6 +819,30 @@ int32_t scint_nanmean_axis_workspace_bytes(int64_t nf, int64_t nt, size_t* SCINT
 int32_t scint_nanmean_axis(const double* a, int64_t nf, int64_t nt, int32_t axis, double* out, void* workspace,
                            size_t workspace_bytes, void* stream);
 int32_t scint_divide_axis(double* a, int64_t nf, int64_t nt, int32_t axis, const double* v, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Biharmonic inpainting of flagged pixels: the method of Dynspec.refill(method='biharmonic') (dynspec.py:3301-3307, scikit-image's
+ * inpaint_biharmonic with split_into_regions=False); kernels in csrc/inpaint.hpp, DESIGN.md 4r.
+ *
+ * scint_inpaint_biharmonic: in place on dyn[nf][nt] (float64, device).  mask[nf][nt] (device, uint8): non-zero = the pixel is
+ *   unknown; nmask = the number of such pixels (the caller counts them: it sizes the workspace; SCINT_E_ARG if the device counts
+ *   another number).  With L the 5-point Laplacian with reflecting edges (scipy.ndimage.laplace, mode='reflect'), m the masked
+ *   and k the other pixels, the masked pixels become the solution of (L^2)_mm u_m = -(L^2)_mk u_k; every other pixel keeps its
+ *   bits, and the values of dyn under the mask are never read (they may be NaN).  stencils[25][5][5] (device): for the class
+ *   5 cf + ct of a pixel (cf, ct = 0, 1: that far from the first channel / sub-integration, 2: interior, 3, 4: one and zero
+ *   from the last) the coefficients of L^2 at the offsets (-2..2, -2..2) around it, zero beyond the edge.
+ *   Solver: conjugate gradients from zero, every scalar on the device, every sum in one fixed order and no atomics: equal inputs
+ *   give equal bits.  It stops when |r|_2 <= tol |b|_2 for the TRUE residual r = b - A u: the recurrence's residual is tested
+ *   every step on the device (the host looks every 8 steps), the true one is formed when that test passes, and the iteration goes
+ *   on from it if it fails.  0 < tol < 1.  SCINT_E_NOCONV after max_iter steps (dyn is then left as it was), SCINT_E_NONFINITE
+ *   if a known pixel within two pixels of a masked one is NaN or inf.  *residual_out (HOST, may be NULL) = the true relative
+ *   residual |b - A u|_2 / |b|_2, *iters_out (HOST, may be NULL) = the steps taken; both are set on SCINT_E_NOCONV too.
+ *   nmask = 0 returns at once.  Limits: nf, nt >= 5 (the 25 classes are distinct), nf nt < 2^31, nmask < nf nt.  Synchronous.
+ *   Workspace: scint_inpaint_biharmonic_workspace_bytes(nf, nt, nmask): 4 nf nt + 52 nmask bytes and 25 KB. */
+int32_t scint_inpaint_biharmonic_workspace_bytes(int64_t nf, int64_t nt, int64_t nmask, size_t* SCINT_HOST bytes);
+int32_t scint_inpaint_biharmonic(double* dyn, int64_t nf, int64_t nt, const uint8_t* mask, int64_t nmask, const double* stencils,
+                                 double tol, int32_t max_iter, double* SCINT_HOST residual_out, int32_t* SCINT_HOST iters_out,
+                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Scaled-time (NuT) conjugate spectrum: scint_utils.slow_FT (scint_utils.py:655-703).  dyn[nt][nf] is [time][frequency], row-major

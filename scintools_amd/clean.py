@@ -11,6 +11,9 @@ method uploads the array once, runs the kernels of ``csrc/clean.hpp`` and downlo
 * ``refill('linear')`` (and ``'biharmonic'``, which falls back to it as the reference does without scikit-image): gaps that are
   whole channels or whole sub-integrations are interpolated across on the device; any other mask raises
   ``NotImplementedError`` (the reference's answer then depends on Qhull's tie-breaking on the regular grid).
+* ``inpaint`` (not in the reference: the biharmonic fill that its ``refill()`` runs by default with scikit-image, for any mask):
+  compaction of the mask, the 25-stencil matrix-free operator and conjugate gradients on the device (``csrc/inpaint.hpp``); the
+  host builds the stencil table and counts the mask.  ``refill`` itself is unchanged and does not call it.
 * ``correct_dyn(svd=True)``: the top ``nmodes`` singular triplets by block iteration on the device, the model and the divide
   too.  ``svd=False``: the two ``nanmean`` s and the divides on the device, ``savgol_filter`` of the two vectors on the host.
 * ``trim_edges``, ``crop_dyn``: host only.
@@ -29,6 +32,8 @@ SVD_TOL = 1e-12            # = ththmod.DEFAULT_TOL (tests/test_clean_cpu.py chec
 SVD_MAX_ITER = 4000
 MAX_MODES = 4              # correct_dyn / svd_model; the kernels carry up to 8 columns (a complex array needs two per mode)
 MEDIAN_MAX_WINDOW = 225    # kf * kt of refill('median') (csrc/clean.hpp, kMedMaxWindow)
+INPAINT_TOL = 1e-12        # = ththmod.DEFAULT_TOL: the true relative residual of the biharmonic fill
+INPAINT_MAX_ITER = 2000    # conjugate-gradient steps of the biharmonic fill (some 50 for isolated pixels and single lines)
 
 _IRREGULAR = ("refill(method={0!r}): only gaps that are whole channels or whole sub-integrations are interpolated on the "
               "device.  For any other mask (isolated pixels, blocks, channels and sub-integrations together) the reference's "
@@ -94,6 +99,86 @@ def linear_fill_device(dyn, axis, line_valid):
     nf, nt = (int(v) for v in t.shape)
     v = device.to_device(np.asarray(line_valid, dtype=np.uint8), torch.uint8)
     _lib.call("scint_refill_linear", t, nf, nt, int(axis), v, device.stream_ptr())
+    return t.cpu().numpy()
+
+
+def stencil_table():
+    """The 25 stencils of the squared Laplacian, [25][5][5]: entry ``5 a + b`` holds, for a pixel of class ``(a, b)`` (per axis 0, 1:
+    that far from the first line, 2: interior, 3, 4: one and zero from the last), the coefficients of ``L @ L`` at the offsets
+    ``-2..2`` x ``-2..2`` around it, zero beyond the edge.  ``L`` is the 5-point Laplacian with reflecting edges.  A 5 x 5 image has
+    one pixel of every class, and a column of ``L @ L`` reaches two pixels, so the table is read off that image."""
+    global _STENCILS
+    if _STENCILS is None:
+        l1 = -2.0 * np.eye(5) + np.eye(5, k=1) + np.eye(5, k=-1)
+        l1[0, 0] = l1[4, 4] = -1.0                      # the reflected neighbour of an edge pixel is the pixel itself
+        lap = np.kron(l1, np.eye(5)) + np.kron(np.eye(5), l1)
+        cols = (lap @ lap).reshape(5, 5, 5, 5)          # [row, column of the image][a, b of the pixel]
+        table = np.zeros((5, 5, 5, 5))
+        for a in range(5):
+            for b in range(5):
+                for dr in range(-2, 3):
+                    for dc in range(-2, 3):
+                        if 0 <= a + dr < 5 and 0 <= b + dc < 5:
+                            table[a, b, dr + 2, dc + 2] = cols[a + dr, b + dc, a, b]
+        _STENCILS = table.reshape(25, 5, 5)
+    return _STENCILS
+
+
+_STENCILS = None
+
+
+def biharmonic_fill_device(dyn, mask=None, tol=INPAINT_TOL, max_iter=None, info=None):
+    """A copy of the 2-D ``dyn`` with the pixels of ``mask`` (default: the non-finite ones) replaced by the biharmonic fill, the
+    method of ``refill(method='biharmonic')`` in the reference (scikit-image's ``inpaint_biharmonic``): with ``L`` the 5-point
+    Laplacian with reflecting edges, ``m`` the masked and ``k`` the known pixels, the solution of ``(L L)_mm u_m = -(L L)_mk u_k``
+    by conjugate gradients on the device (``scint_inpaint_biharmonic``, csrc/inpaint.hpp) down to a true relative residual of
+    ``tol``.  Known pixels keep their bits.  ``info`` receives ``iters``, ``residual`` (the true relative residual) and ``nmask``.
+
+    ``max_iter`` (default ``INPAINT_MAX_ITER``) bounds the steps; ``ScintHipError`` when they run out.  The condition number grows
+    with the fourth power of the widest gap and the steps with its square root: isolated pixels and single lines take some 50
+    steps, a gap 40 pixels wide will not finish within the default."""
+    out = np.array(dyn, dtype=np.float64)
+    if out.ndim != 2:
+        raise ValueError("biharmonic_fill_device needs a 2-D array")
+    bad = ~is_valid(out) if mask is None else np.asarray(mask, dtype=bool)
+    if bad.shape != out.shape:
+        raise ValueError(f"biharmonic_fill_device: the mask has shape {bad.shape}, the array {out.shape}")
+    nf, nt = out.shape
+    nmask = int(np.count_nonzero(bad))
+    if info is not None:
+        info.update(iters=0, residual=0.0, nmask=nmask)
+    if nmask == 0:
+        return out
+    if nmask == bad.size:
+        raise ValueError("biharmonic_fill_device: every pixel is masked, there is nothing to fill from")
+    if nf < 5 or nt < 5:
+        raise ValueError(f"biharmonic_fill_device: a {nf} x {nt} array; the 25 edge classes of the stencil need at least 5 x 5")
+    if not is_valid(out[~bad]).all():
+        raise ValueError("biharmonic_fill_device: a pixel outside the mask is not finite")
+    if not 0.0 < tol < 1.0:
+        raise ValueError("biharmonic_fill_device: tol must lie between 0 and 1")
+    max_iter = INPAINT_MAX_ITER if max_iter is None else int(max_iter)
+    if max_iter < 1:
+        raise ValueError("biharmonic_fill_device: max_iter must be at least 1")
+    _lib_ready()
+    t = device.to_device(out, torch.float64)
+    m = device.to_device(bad, torch.uint8)
+    table = device.to_device(stencil_table(), torch.float64)
+    ws = device.workspace_for("scint_inpaint_biharmonic", nf, nt, nmask)
+    residual, iters = ctypes.c_double(), ctypes.c_int32()
+    try:
+        _lib.call("scint_inpaint_biharmonic", t, nf, nt, m, nmask, table, tol, max_iter, residual, iters, ws, ws.numel(),
+                  device.stream_ptr())
+    except _lib.ScintHipError as err:
+        if err.status == _lib.SCINT_E_NOCONV:
+            noconv = _lib.ScintHipError(f"biharmonic_fill_device: conjugate gradients stopped after {iters.value} steps at a relative "
+                                        f"residual of {residual.value:.3g} (wanted {tol:g}): a wide gap (the condition number grows "
+                                        "with the fourth power of its width); raise max_iter")
+            noconv.status = err.status
+            raise noconv from None
+        raise
+    if info is not None:
+        info.update(iters=iters.value, residual=residual.value)
     return t.cpu().numpy()
 
 
@@ -231,6 +316,15 @@ def refill(self, method='biharmonic', zeros=True, kernel_size=5, linear=True):
             self.dyn = linear_fill_device(self.dyn, *found)
     # every method ends with the mean of the valid pixels in whatever is still NaN (gaps at an edge, linear=False)
     np.copyto(self.dyn, np.mean(self.dyn[is_valid(self.dyn)]), where=np.isnan(self.dyn))
+
+
+def inpaint(self, zeros=True, tol=INPAINT_TOL):
+    """Replace the non-finite pixels (and with ``zeros`` the zeros, as ``refill`` does) of the dynamic spectrum by the biharmonic
+    fill, in place: what the reference's ``refill()`` computes by default where scikit-image is installed.  Any mask is accepted:
+    isolated pixels, blocks, whole channels and sub-integrations together.  See ``biharmonic_fill_device``."""
+    if zeros:
+        np.copyto(self.dyn, np.nan, where=(self.dyn == 0))
+    np.copyto(self.dyn, biharmonic_fill_device(self.dyn, tol=tol))
 
 
 def _without_zeros(vec):

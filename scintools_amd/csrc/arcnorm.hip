@@ -8,6 +8,7 @@
 //   scint_scattered_image  Dynspec.calc_scattered_image        dynspec.py:3553-3570 (kernels: scatim.hpp)
 //   scint_zap, scint_refill_median / _linear, scint_svd_model, scint_nanmean_axis, scint_divide_axis
 //                          Dynspec.zap / refill / correct_dyn   dynspec.py:3856-3870, 3273-3410 (kernels: clean.hpp)
+//   scint_inpaint_biharmonic  Dynspec.inpaint: the biharmonic fill of refill   dynspec.py:3301-3307 (kernels: inpaint.hpp)
 //
 // Everything here is HBM-bound streaming work (a gather along each delay row, column and row
 // reductions).  Compiled with -ffp-contract=off: the interpolation must round like NumPy's
@@ -306,6 +307,7 @@ block_moment_final_kernel(const double* partial, int np, double inv_n, int take_
 
 #include "scatim.hpp"
 #include "clean.hpp"
+#include "inpaint.hpp"
 
 using namespace scint;
 
@@ -653,6 +655,119 @@ extern "C" int32_t scint_divide_axis(double* a, int64_t nf, int64_t nt, int32_t 
     SCINT_REQUIRE(nf >= 1 && nt >= 1 && (axis == 0 || axis == 1), "divide_axis: bad arguments");
     hipLaunchKernelGGL(clean_divide_kernel, dim3((unsigned)ceil_div(nt, 256), (unsigned)std::min<int64_t>(nf, 65535)), dim3(256), 0,
                        (hipStream_t)stream_, a, nf, nt, (int)axis, v);
+    SCINT_LAUNCH_CHECK();
+    return SCINT_OK;
+}
+
+// ------------------------------------------------------------------------------
+// biharmonic inpainting (kernels: inpaint.hpp)
+// ------------------------------------------------------------------------------
+extern "C" int32_t scint_inpaint_biharmonic_workspace_bytes(int64_t nf, int64_t nt, int64_t nmask, size_t* bytes) {
+    SCINT_REQUIRE(bytes && nf >= 1 && nt >= 1 && nmask >= 0 && nmask <= nf * nt, "inpaint_biharmonic_workspace_bytes: bad arguments");
+    const size_t npix = (size_t)nf * (size_t)nt, n = (size_t)std::max<int64_t>(nmask, 1);
+    *bytes = align_up(sizeof(int32_t) * npix, 256) + align_up(sizeof(int32_t) * n, 256) +
+             align_up(sizeof(int32_t) * (size_t)ceil_div((int64_t)npix, kInpaintChunk), 256) + 6 * align_up(sizeof(double) * n, 256) +
+             align_up(sizeof(double) * 3 * kCgMaxBlocks, 256) + 512;
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_inpaint_biharmonic(double* dyn, int64_t nf, int64_t nt, const uint8_t* mask, int64_t nmask,
+                                            const double* stencils, double tol, int32_t max_iter, double* residual_out,
+                                            int32_t* iters_out, void* workspace, size_t workspace_bytes, void* stream_) {
+    SCINT_REQUIRE(dyn && mask && stencils && workspace, "inpaint_biharmonic: null pointer");
+    SCINT_REQUIRE(nf >= 5 && nt >= 5, "inpaint_biharmonic: the 25 stencil classes need nf >= 5 and nt >= 5");
+    SCINT_REQUIRE(nf * nt < (int64_t(1) << 31), "inpaint_biharmonic: more than 2^31 - 1 pixels");
+    SCINT_REQUIRE(nmask >= 0 && nmask < nf * nt, "inpaint_biharmonic: every pixel is masked (or a negative count)");
+    SCINT_REQUIRE(tol > 0.0 && tol < 1.0 && max_iter >= 1, "inpaint_biharmonic: bad tolerance or iteration limit");
+    if (residual_out) *residual_out = 0.0;
+    if (iters_out) *iters_out = 0;
+    if (nmask == 0) return SCINT_OK;
+    size_t need = 0;
+    scint_inpaint_biharmonic_workspace_bytes(nf, nt, nmask, &need);
+    if (workspace_bytes < need) { set_error("scint: inpaint_biharmonic workspace too small"); return SCINT_E_WORKSPACE; }
+    hipStream_t stream = (hipStream_t)stream_;
+    const int64_t npix = nf * nt, nchunk = ceil_div(npix, kInpaintChunk), n = nmask;
+    const int nb = (int)std::min<int64_t>(kCgMaxBlocks, ceil_div(n, 256));
+    Carver carve(workspace, workspace_bytes);
+    int32_t* index = carve.take<int32_t>((size_t)npix);
+    int32_t* list = carve.take<int32_t>((size_t)n);
+    int32_t* counts = carve.take<int32_t>((size_t)nchunk);
+    double* x = carve.take<double>((size_t)n);
+    double* r = carve.take<double>((size_t)n);
+    double* b = carve.take<double>((size_t)n);
+    double* q = carve.take<double>((size_t)n);
+    double* P[2] = {carve.take<double>((size_t)n), carve.take<double>((size_t)n)};
+    double* part = carve.take<double>((size_t)3 * kCgMaxBlocks);
+    double* RR[2] = {part, part + kCgMaxBlocks};
+    double* pq = part + 2 * kCgMaxBlocks;
+    InpaintState* st = carve.take<InpaintState>(1);
+    InpaintState h;
+#define SCINT_INPAINT_READ()                                                                         \
+    do {                                                                                             \
+        SCINT_HIP(hipMemcpyAsync(&h, st, sizeof(InpaintState), hipMemcpyDeviceToHost, stream));      \
+        SCINT_HIP(hipStreamSynchronize(stream));                                                     \
+    } while (0)
+
+    // the unknowns, in pixel order
+    hipLaunchKernelGGL(inpaint_count_kernel, dim3((unsigned)nchunk), dim3(256), 0, stream, mask, npix, counts);
+    SCINT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(inpaint_scan_kernel, dim3(1), dim3(256), 0, stream, counts, nchunk, st);
+    SCINT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(inpaint_fill_kernel, dim3((unsigned)nchunk), dim3(256), 0, stream, mask, npix, (const int32_t*)counts, n, index,
+                       list);
+    SCINT_LAUNCH_CHECK();
+    SCINT_HIP(hipMemcpyAsync(&h.count, &st->count, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    SCINT_HIP(hipStreamSynchronize(stream));
+    SCINT_REQUIRE(h.count == n, "inpaint_biharmonic: nmask is not the number of non-zero elements of the mask");
+
+    hipLaunchKernelGGL(inpaint_rhs_kernel, dim3(nb), dim3(256), 0, stream, (const double*)dyn, nf, nt, stencils, (const int32_t*)index,
+                       (const int32_t*)list, n, b, r, x, RR[0]);
+    SCINT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(inpaint_init_kernel, dim3(1), dim3(256), 0, stream, (const double*)RR[0], nb, tol, st);
+    SCINT_LAUNCH_CHECK();
+    SCINT_INPAINT_READ();
+    if (!(h.bnorm2 - h.bnorm2 == 0.0)) {
+        set_error("scint: inpaint_biharmonic: a known pixel next to a masked one is not finite");
+        return SCINT_E_NONFINITE;
+    }
+    bool ok = h.bnorm2 == 0.0;                          // b = 0: the fill is zero
+    int it = 0, par = 0, first = 1;
+    while (!ok) {
+        for (int s = 0; s < kCgCheck && it < max_iter; ++s) {
+            ++it;
+            hipLaunchKernelGGL(inpaint_ap_kernel, dim3(nb), dim3(256), 0, stream, nf, nt, stencils, (const int32_t*)index,
+                               (const int32_t*)list, n, (const double*)r, (const double*)P[par], P[par ^ 1], q, (const double*)RR[par],
+                               (const double*)RR[par ^ 1], nb, first, it, pq, st);
+            SCINT_LAUNCH_CHECK();
+            hipLaunchKernelGGL(inpaint_update_kernel, dim3(nb), dim3(256), 0, stream, n, (const double*)P[par ^ 1], (const double*)q,
+                               (const double*)pq, nb, x, r, RR[par ^ 1], st);
+            SCINT_LAUNCH_CHECK();
+            par ^= 1;
+            first = 0;
+        }
+        hipLaunchKernelGGL(inpaint_probe_kernel, dim3(1), dim3(256), 0, stream, (const double*)RR[par], nb, 0, st);
+        SCINT_LAUNCH_CHECK();
+        SCINT_INPAINT_READ();
+        if (!(h.rho - h.rho == 0.0)) { set_error("scint: inpaint_biharmonic: the residual is not finite"); return SCINT_E_NONFINITE; }
+        if (!h.done_a && it < max_iter) continue;
+        // within the bound by the recurrence (or out of steps): the true residual b - A x decides
+        hipLaunchKernelGGL(inpaint_true_kernel, dim3(nb), dim3(256), 0, stream, nf, nt, stencils, (const int32_t*)index,
+                           (const int32_t*)list, n, (const double*)b, (const double*)x, r, RR[0], st);
+        SCINT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(inpaint_probe_kernel, dim3(1), dim3(256), 0, stream, (const double*)RR[0], nb, 1, st);
+        SCINT_LAUNCH_CHECK();
+        SCINT_INPAINT_READ();
+        ok = h.done_a != 0;
+        it = h.iters;                                   // the steps that did work
+        par = 0;
+        first = 1;                                      // continue from the true residual: p = r
+        if (it >= max_iter) break;
+    }
+#undef SCINT_INPAINT_READ
+    if (iters_out) *iters_out = h.iters;
+    if (residual_out) *residual_out = h.bnorm2 > 0.0 ? sqrt(h.true_rho / h.bnorm2) : 0.0;
+    if (!ok) { set_error("scint: inpaint_biharmonic: conjugate gradients did not reach the residual"); return SCINT_E_NOCONV; }
+    hipLaunchKernelGGL(inpaint_scatter_kernel, dim3(nb), dim3(256), 0, stream, (const double*)x, (const int32_t*)list, n, dyn);
     SCINT_LAUNCH_CHECK();
     return SCINT_OK;
 }

@@ -19,7 +19,8 @@ reference ``Dynspec``, or plain arrays) with
 
 * ``trim_edges``, ``crop_dyn``, ``zap``, ``refill``, ``correct_dyn``, ``auto_processing`` (dynspec.py:259-328, 3816-3870,
   3273-3410, 422-440): the cleaning chain; medians, the median filter, gap interpolation and the truncated SVD run on the GPU
-  (``scintools_amd/clean.py``).
+  (``scintools_amd/clean.py``).  ``inpaint`` (not in the reference) is the biharmonic fill of ``refill``'s default method, for
+  any mask, by conjugate gradients on the GPU.
 
 * ``calc_acf``, ``get_scint_params(method='nofit')``, ``get_acf_tilt``, ``cut_dyn`` (dynspec.py:3750-3814, 2470-2648,
   2283-2413, 3158-3271): the ACF stays in HBM; the scintillation scales, the ACF tilt and the segment stacks read what they need
@@ -296,6 +297,7 @@ class Dynspec:
     crop_dyn = clean.crop_dyn
     zap = clean.zap
     refill = clean.refill
+    inpaint = clean.inpaint
     correct_dyn = clean.correct_dyn
     auto_processing = clean.auto_processing
 
