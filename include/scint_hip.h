@@ -57,7 +57,7 @@ extern "C" {
  *   108: scint_two_curve_map / scint_sv_sweep_multi (the thin-screen search, scint_thin_geom);
  *   (the VLBI entry points -- scint_cs_complex_batch / scint_vlbi_composite / scint_eigh_top_batch -- and the batched 1-D ACF fit --
  *   scint_acf1d_fit -- and the approximate 2-D one -- scint_acf2d_approx_fit -- and the biharmonic fill -- scint_inpaint_biharmonic --
- *   only ADD symbols: no bump; a build without them fails at load, which checks every declared symbol) */
+ *   and the ACFs and secondary spectra of a stack -- scint_acf_batch, scint_sspec_batch -- only ADD symbols: no bump; a build without them fails at load, which checks every declared symbol) */
 #define SCINT_ABI_VERSION 108
 
 #define SCINT_OK 0
@@ -129,6 +129,22 @@ int32_t scint_sspec(const double* dyn, int64_t nf, int64_t nt,
                     const double* pd_fd, const double* pd_td,
                     double* sec_out, void* workspace, size_t workspace_bytes,
                     void* stream);
+
+/* scint_sspec of every problem of a stack: sec_out[b][rows][ncfft] (rows = nrfft / 2 if halve, else nrfft) holds, BIT FOR BIT, what
+ * scint_sspec writes for stack[b][nf][nt] with the same windows, prewhite, halve and post-darkening vectors (b < B, 1 <= B <=
+ * 65535): each problem's own mean and windowed mean, then prewhitening, |.|^2, post-darkening, 10 log10 and fftshift as there.
+ * Problems whose padded half-length is below 256 on either axis (nf <= 128 or nt <= 128, or halve = 0) go through scint_sspec's
+ * generic transform as slots / grid.z of the same kernels and its reductions in their fixed order: the number of launches does
+ * not depend on B, and the workspace grows with B.  Larger problems (both half-lengths 256 .. 8192, halve = 1) are scint_sspec's
+ * persistent kernels, which take one problem at a time: they run problem after problem on ONE problem's workspace, and their
+ * launches grow with B.  No atomics.  Asynchronous on `stream`. */
+int32_t scint_sspec_batch_workspace_bytes(int64_t B, int64_t nf, int64_t nt, int32_t halve, size_t* SCINT_HOST bytes);
+int32_t scint_sspec_batch(const double* stack, int64_t B, int64_t nf, int64_t nt,
+                          const double* win_t, const double* win_f,
+                          int32_t prewhite, int32_t halve,
+                          const double* pd_fd, const double* pd_td,
+                          double* sec_out, void* workspace, size_t workspace_bytes,
+                          void* stream);
 
 /* ---- conjugate spectrum: single_search lines ththmod.py:777-787 ---------- */
 /* CS = fftshift(fft2(pad(dspec, right/bottom by npad*shape, pad_value)));
@@ -450,6 +466,17 @@ int32_t scint_gerchberg_saxton(scint_c128* wavefield, int64_t rows, int64_t cols
 int32_t scint_acf_workspace_bytes(int64_t nf, int64_t nt, size_t* SCINT_HOST bytes);
 int32_t scint_acf(const double* dyn, int64_t nf, int64_t nt, int32_t subtract_mean, int32_t normalise,
                   double* acf_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* scint_acf of every problem of a stack: acf_out[b][2nf][2nt] holds, BIT FOR BIT, what scint_acf writes for stack[b][nf][nt]
+ * (b < B, 1 <= B <= 65535) -- each problem's own mean when subtract_mean, its own maximum when normalise, and for a degenerate
+ * problem (a constant one with subtract_mean: an all-zero ACF, then 0 / 0) what scint_acf gives.  The problems go through
+ * scint_acf's row and column passes as slots / grid.z of the same kernels and through its reductions in their fixed order, so the
+ * number of launches does not depend on B; no atomics.  The workspace grows with B (the complex intermediates: 16 * 2nf * 2nt
+ * bytes per problem and array); a caller that has to bound it splits the stack and asks scint_acf_batch_workspace_bytes for each
+ * part's need.  Asynchronous on `stream`. */
+int32_t scint_acf_batch_workspace_bytes(int64_t B, int64_t nf, int64_t nt, size_t* SCINT_HOST bytes);
+int32_t scint_acf_batch(const double* stack, int64_t B, int64_t nf, int64_t nt, int32_t subtract_mean, int32_t normalise,
+                        double* acf_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Dynspec.calc_acf(method='sspec') (dynspec.py:3798-3807) from the full-frame (halve = 0, prewhite = 0) secondary spectrum in dB
  * sec_db[R][C] of scint_sspec: acf_out[R][C] = real(fftshift(fft2(10**(fftshift(sec_db) / 10)))), / max if normalise.  R >= 2 and

@@ -162,9 +162,10 @@ constexpr int kRedBlocks = 1024;
 
 // Stage 1 of the deterministic reductions.  Every thread keeps four independent running sums
 // (four loads in flight, combined in a fixed order at the end).
+// (The bodies are functions of their own: the kernels of a STACK of problems, further down, run them once per problem -- grid.y --
+// on that problem's values and partials, so a problem's sums are added in the order of the call that takes it alone.)
 template <class F>
-__global__ void __launch_bounds__(256) reduce_partial_kernel(F f, int64_t n, double* partial) {
-    __shared__ double red[4];
+__device__ inline void reduce_partial_body(F f, int64_t n, double* partial, double* red) {
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -174,6 +175,11 @@ __global__ void __launch_bounds__(256) reduce_partial_kernel(F f, int64_t n, dou
     for (; i < n; i += stride) a0 += f(i);
     const double acc = block_sum((a0 + a1) + (a2 + a3), red);
     if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+}
+template <class F>
+__global__ void __launch_bounds__(256) reduce_partial_kernel(F f, int64_t n, double* partial) {
+    __shared__ double red[4];
+    reduce_partial_body(f, n, partial, red);
 }
 
 // The same over a [nrows, ncols] array for functors that need (row, col): block b takes rows
@@ -194,22 +200,24 @@ __global__ void __launch_bounds__(256) reduce2d_partial_kernel(F f, int64_t nrow
 }
 
 // out[0] = scale * sum(partial[0..np))   (fixed order)
-__global__ void __launch_bounds__(256) reduce_final_kernel(const double* partial, int np,
-                                                           double scale, double* out) {
-    __shared__ double red[4];
+__device__ inline void reduce_final_body(const double* partial, int np, double scale, double* out, double* red) {
     double acc = 0.0;
     for (int i = threadIdx.x; i < np; i += blockDim.x) acc += partial[i];
     acc = block_sum(acc, red);
     if (threadIdx.x == 0) out[0] = acc * scale;
 }
+__global__ void __launch_bounds__(256) reduce_final_kernel(const double* partial, int np,
+                                                           double scale, double* out) {
+    __shared__ double red[4];
+    reduce_final_body(partial, np, scale, out, red);
+}
 
 // Both means calc_sspec needs (dynspec.py:3667-3674) in ONE pass over the dynamic spectrum:
 //   m1 = mean(dyn),   m2 = mean(w_f[r] w_t[c] (dyn - m1)) = (S_wd - m1 S_w) / n
 // with S_wd = sum w_f w_t dyn and S_w = sum w_f w_t: three fixed-order sums, then the scalars.
-__global__ void __launch_bounds__(256) sspec_sums_kernel(const double* __restrict__ dyn, const double* __restrict__ wt,
-                                                         const double* __restrict__ wf, int64_t nf, int64_t nt,
-                                                         double* partial /*3 x gridDim.x*/) {
-    __shared__ double red[4];
+__device__ inline void sspec_sums_body(const double* __restrict__ dyn, const double* __restrict__ wt,
+                                       const double* __restrict__ wf, int64_t nf, int64_t nt,
+                                       double* partial /*3 x gridDim.x*/, double* red) {
     double sd = 0.0, swd = 0.0, sw = 0.0;
     for (int64_t r = blockIdx.x; r < nf; r += gridDim.x) {
         const double fr = wf ? wf[r] : 1.0;
@@ -225,8 +233,13 @@ __global__ void __launch_bounds__(256) sspec_sums_kernel(const double* __restric
         partial[blockIdx.x] = sd; partial[gridDim.x + blockIdx.x] = swd; partial[2 * gridDim.x + blockIdx.x] = sw;
     }
 }
-__global__ void __launch_bounds__(256) sspec_means_kernel(const double* partial, int np, double n, double* scal) {
+__global__ void __launch_bounds__(256) sspec_sums_kernel(const double* __restrict__ dyn, const double* __restrict__ wt,
+                                                         const double* __restrict__ wf, int64_t nf, int64_t nt,
+                                                         double* partial /*3 x gridDim.x*/) {
     __shared__ double red[4];
+    sspec_sums_body(dyn, wt, wf, nf, nt, partial, red);
+}
+__device__ inline void sspec_means_body(const double* partial, int np, double n, double* scal, double* red) {
     double sd = 0.0, swd = 0.0, sw = 0.0;
     for (int i = threadIdx.x; i < np; i += 256) { sd += partial[i]; swd += partial[np + i]; sw += partial[2 * np + i]; }
     sd = block_sum(sd, red); swd = block_sum(swd, red); sw = block_sum(sw, red);
@@ -236,11 +249,33 @@ __global__ void __launch_bounds__(256) sspec_means_kernel(const double* partial,
         scal[1] = (swd - m1 * sw) / n;
     }
 }
+__global__ void __launch_bounds__(256) sspec_means_kernel(const double* partial, int np, double n, double* scal) {
+    __shared__ double red[4];
+    sspec_means_body(partial, np, n, scal, red);
+}
+// The same for a stack dyn[B][nf][nt]: problem blockIdx.y with the single problem's grid.x, its partials 3 * gridDim.x apart, its two
+// means at scal[2 b], scal[2 b + 1] -- the sums of a problem are added in the order of the call that takes it alone.
+__global__ void __launch_bounds__(256) sspec_stack_sums_kernel(const double* __restrict__ dyn, const double* __restrict__ wt,
+                                                               const double* __restrict__ wf, int64_t nf, int64_t nt,
+                                                               double* partial /*B x 3 x gridDim.x*/) {
+    __shared__ double red[4];
+    sspec_sums_body(dyn + (int64_t)blockIdx.y * nf * nt, wt, wf, nf, nt, partial + (int64_t)blockIdx.y * 3 * gridDim.x, red);
+}
+__global__ void __launch_bounds__(256) sspec_stack_means_kernel(const double* partial, int np, double n, double* scal) {
+    __shared__ double red[4];
+    sspec_means_body(partial + (int64_t)blockIdx.y * 3 * np, np, n, scal + 2 * blockIdx.y, red);
+}
+
+// workgroups of a two-stage reduction over n values: a sum (launch_reduce) and the maximum of an ACF.  The stack kernels use
+// the same counts, which is what gives a problem of a stack the partials -- and the bits -- of the single call.
+static int reduce_blocks(int64_t n) { return (int)std::min<int64_t>(kRedBlocks, std::max<int64_t>(1, ceil_div(n, 256 * 4))); }
+static int max_blocks(int64_t n) { return (int)std::min<int64_t>(kRedBlocks, std::max<int64_t>(1, ceil_div(n, 1024))); }
+static int sspec_sums_blocks(int64_t nf) { return (int)std::min<int64_t>(kRedBlocks, nf); }
 
 template <class F>
 static int32_t launch_reduce(F f, int64_t n, double scale, double* partial /*kRedBlocks*/,
                              double* out, hipStream_t stream) {
-    int blocks = (int)std::min<int64_t>(kRedBlocks, std::max<int64_t>(1, ceil_div(n, 256 * 4)));
+    const int blocks = reduce_blocks(n);
     hipLaunchKernelGGL((reduce_partial_kernel<F>), dim3(blocks), dim3(256), 0, stream, f, n, partial);
     SCINT_LAUNCH_CHECK();
     hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(256), 0, stream, partial, blocks, scale, out);
@@ -312,7 +347,8 @@ __device__ inline int shift_half(int i, int n) {
 }
 
 enum SrcMode { SRC_ARRAY = 0, SRC_SSPEC = 1, SRC_CS = 2, SRC_MODEL = 3, SRC_MULCONJ = 4, SRC_CONJ = 5,
-               SRC_ACF_IN = 6, SRC_POWER = 7, SRC_CPAD = 8, SRC_DBPOWER = 9, SRC_ROLL = 10 };
+               SRC_ACF_IN = 6, SRC_POWER = 7, SRC_CPAD = 8, SRC_DBPOWER = 9, SRC_ROLL = 10,
+               SRC_SSPEC_STACK = 11 };
 
 // Element (row, j) of the row-FFT input, j in [0, fft length).
 struct RowSource {
@@ -332,6 +368,13 @@ struct RowSource {
     // SRC_ROLL: x[(r + roll_r) % R][(j + roll_c) % C] of a real x = wv.dyn (roll_real) or a complex x = a: fftshift is a roll by
     // n - n/2, ifftshift one by n/2 -- they differ on odd lengths (scint_fft2_any)
     int roll_r, roll_c, roll_real;
+    // SRC_ACF_IN on a stack of problems (rows b * prob_rows + r of wv.dyn are problem b's): the mean of row r is
+    // wv.m1[r / prob_rows]; 0: one problem, wv.m1[0].  (SRC_POWER needs no more than the stacked rows: it has no scalar.)
+    int prob_rows;
+    // SRC_SSPEC_STACK: SRC_SSPEC of a stack wv.dyn[B][prob_src_rows][wv.nt].  Row r is row r % prob_rows of problem b = r / prob_rows
+    // (prob_rows = prob_src_rows - 1 under prewhitening: the stencil reads one row further, inside the problem); the problem's
+    // two means are wv.m1[2 b] and wv.m1[2 b + 1], the windows are shared.  The arithmetic on a value is SRC_SSPEC's.
+    int prob_src_rows;
 
     __device__ inline double sspec_d(int r, int c) const { return wv.at(r, c) - m2[0]; }
 
@@ -345,7 +388,7 @@ struct RowSource {
             case SRC_MULCONJ: v = conj(a[(int64_t)r * ld + j] * b[j]); break;
             case SRC_CONJ: v = conj(a[(int64_t)r * ld + j]); break;
             case SRC_ACF_IN:   // (dyn - mean) zero-padded on the right (dynspec.py:3783-3790)
-                v = mk(j < wv.nt ? wv.dyn[(int64_t)r * wv.nt + j] - wv.m1[0] : 0.0, 0.0);
+                v = mk(j < wv.nt ? wv.dyn[(int64_t)r * wv.nt + j] - wv.m1[prob_rows > 0 ? r / prob_rows : 0] : 0.0, 0.0);
                 break;
             case SRC_POWER: {  // |X|^2 (dynspec.py:3791-3792); real, so no conjugation is needed
                 const cplx x = a[(int64_t)r * ld + j];
@@ -361,6 +404,18 @@ struct RowSource {
                 else  // convolve2d([[1,-1],[-1,1]], dyn, 'valid')  (dynspec.py:3681)
                     v = mk(sspec_d(r + 1, j + 1) - sspec_d(r + 1, j) - sspec_d(r, j + 1) + sspec_d(r, j), 0.0);
                 break;
+            case SRC_SSPEC_STACK: {
+                const int pb = r / prob_rows, rr = r - pb * prob_rows;
+                WindowedValue w = wv;
+                w.dyn += (int64_t)pb * prob_src_rows * wv.nt;
+                w.m1 += 2 * pb;
+                const double mean2 = w.m1[1];
+                auto d = [&](int a, int c) { return w.at(a, c) - mean2; };
+                if (j >= nt_eff) v = mk(0.0, 0.0);
+                else if (!prewhite) v = mk(d(rr, j), 0.0);
+                else v = mk(d(rr + 1, j + 1) - d(rr + 1, j) - d(rr, j + 1) + d(rr, j), 0.0);
+                break;
+            }
             case SRC_CS: v = mk(j < wv.nt ? wv.dyn[(int64_t)r * wv.nt + j] : pad, 0.0); break;
             case SRC_CPAD: v = j < wv.nt ? a[(int64_t)r * wv.nt + j] : mk(0.0, 0.0); break;
             case SRC_ROLL: {
@@ -710,15 +765,81 @@ struct PairRows {
     }
 };
 struct PairSplitSource {
-    const cplx* z; int ld; int C; int nvalid; double fill0;
+    const cplx* a; int ld; int C; int nvalid; double fill0;
     __device__ inline cplx operator()(int64_t, int r, int c) const {
         if (r >= nvalid) return mk(c == 0 ? fill0 : 0.0, 0.0);
-        const cplx* row = z + (int64_t)(r >> 1) * ld;
+        const cplx* row = a + (int64_t)(r >> 1) * ld;
         const cplx zk = row[c], zc = conj(row[c == 0 ? 0 : C - c]);
         return (r & 1) ? mk(0.5 * (zk.y - zc.y), -0.5 * (zk.x - zc.x))
                        : mk(0.5 * (zk.x + zc.x), 0.5 * (zk.y + zc.y));
     }
 };
+
+// ------------------------------------------------------------------------------
+// a stack of B equal problems through the same kernels
+// ------------------------------------------------------------------------------
+// The transform bodies do not change: a problem is a range of slots of the row kernel and a grid.z of the column kernel.  The
+// source sees the stack as one tall array (row b * nrows + r is row r of problem b) and so does every intermediate; what
+// follows only decodes the problem where a single problem's addressing would cross into its neighbour:
+//   StackPairLoad / StackPairStore / StackPairRows   the pairs of real rows are formed INSIDE a problem (slot s is pair s % npairs
+//       of problem s / npairs), so a problem with an odd number of rows leaves its last row unpaired, as it does alone;
+//   StackFirst / StackSink   problem bt of a column pass reads / writes `stride` elements further on.
+// The arithmetic on a value is that of the wrapped functor: equal inputs give the bits of the single call.
+template <class Src>
+struct StackPairLoad {
+    Src in; int nrows, npairs;
+    struct Slot {
+        const StackPairLoad& p; int r0; bool two;
+        __device__ inline cplx operator()(int j) const { return mk(p.in(r0, j).x, two ? p.in(r0 + 1, j).x : 0.0); }
+    };
+    __device__ inline Slot open(int64_t s) const {
+        const int b = (int)s / npairs, q = (int)s - b * npairs;
+        return Slot{*this, b * nrows + 2 * q, 2 * q + 1 < nrows};
+    }
+};
+struct StackPairStore {
+    static constexpr bool kPair = true;
+    cplx* a; int ld; int nrows, npairs;
+    using Slot = PairStore::Slot;
+    __device__ inline Slot open(int64_t s) const {
+        const int b = (int)s / npairs, q = (int)s - b * npairs;
+        cplx* r0 = a + (int64_t)(b * nrows + 2 * q) * ld;
+        return Slot{r0, 2 * q + 1 < nrows ? r0 + ld : nullptr};
+    }
+};
+template <class Src>
+struct StackPairRows {
+    Src in; int nrows, npairs;
+    __device__ inline cplx operator()(int s, int j) const {
+        const int b = s / npairs, q = s - b * npairs, r0 = b * nrows + 2 * q;
+        return mk(in(r0, j).x, 2 * q + 1 < nrows ? in(r0 + 1, j).x : 0.0);
+    }
+};
+template <class First>
+struct StackFirst {
+    First f; int64_t stride;
+    __device__ inline cplx operator()(int64_t bt, int r, int c) const {
+        First g = f;
+        g.a += bt * stride;
+        return g(bt, r, c);
+    }
+};
+template <int M = -1>      // (M: the sink's mode at compile time, as ColSinkM -- the instantiation the single call runs for that mode)
+struct StackSink {
+    ColSink s; int64_t stride;
+    __device__ inline void operator()(int64_t bt, int k1, int c, cplx v) const {
+        ColSink t = s;      // (the sink's mode uses one of the two outputs; the caller leaves the other null)
+        if (t.out_c) t.out_c += bt * stride;
+        if (t.out_d) t.out_d += bt * stride;
+        t.template put<M>(k1, c, v);
+    }
+};
+// f(stacked sink): the modes with_sink instantiates get the same instantiation here
+template <class F>
+static int32_t with_stack_sink(const ColSink& s, int64_t stride, F&& f) {
+    if (s.mode == SINK_SSPEC) return f(StackSink<SINK_SSPEC>{s, stride});
+    return f(StackSink<>{s, stride});
+}
 
 // ------------------------------------------------------------------------------
 // generic 2-D driver
@@ -731,7 +852,8 @@ struct Fft2Plan {
     size_t off_rowA, off_rowB, off_colA, off_colB, total;   // workspace carve (bytes)
 };
 
-static Fft2Plan make_plan(int64_t R, int64_t C, int64_t nvalid) {
+// (B > 1: a stack of B problems; every buffer then holds the B problems' arrays one after the other)
+static Fft2Plan make_plan(int64_t R, int64_t C, int64_t nvalid, int64_t B = 1) {
     Fft2Plan p;
     p.R = R; p.C = C; p.nvalid = nvalid;
     p.blue_r = !is_pow2(R);
@@ -741,11 +863,11 @@ static Fft2Plan make_plan(int64_t R, int64_t C, int64_t nvalid) {
     size_t off = 0;
     auto take = [&](size_t elems) { off = align_up(off, 256); size_t o = off; off += elems * sizeof(cplx); return o; };
     // row result [nvalid][mC]; Bluestein rows need a second buffer of the same size
-    p.off_rowA = take((size_t)nvalid * (size_t)p.mC);
-    p.off_rowB = p.blue_c ? take((size_t)nvalid * (size_t)p.mC) : p.off_rowA;
+    p.off_rowA = take((size_t)B * (size_t)nvalid * (size_t)p.mC);
+    p.off_rowB = p.blue_c ? take((size_t)B * (size_t)nvalid * (size_t)p.mC) : p.off_rowA;
     // column working array [mR][C]; Bluestein columns need a second one
-    p.off_colA = take((size_t)p.mR * (size_t)C);
-    p.off_colB = p.blue_r ? take((size_t)p.mR * (size_t)C) : p.off_colA;
+    p.off_colA = take((size_t)B * (size_t)p.mR * (size_t)C);
+    p.off_colB = p.blue_r ? take((size_t)B * (size_t)p.mR * (size_t)C) : p.off_colA;
     p.total = align_up(off, 256);
     return p;
 }
@@ -756,12 +878,19 @@ static Fft2Plan make_plan(int64_t R, int64_t C, int64_t nvalid) {
 // real_input: the source is real -> real-to-complex path when both lengths are powers of two:
 //   two rows per row-FFT, only columns 0..C/2 go through the column passes, and the sink emits
 //   each value together with its conjugate-symmetric partner.
+// stack: 0 one problem, the kernels it always ran.  B >= 1: B problems in the same number of launches (the functors above);
+//   the source addresses row b * nvalid + r for row r of problem b, the sink's output moves on by sink_stride elements per
+//   problem, and every problem takes the route -- and so gets the bits -- it takes alone.
 static int32_t fft2_general(RowSource src, int64_t nvalid, double fill0, int64_t R, int64_t C,
                             ColSink sink, void* workspace, size_t workspace_bytes, hipStream_t stream,
-                            bool real_input = false) {
+                            bool real_input = false, int64_t stack = 0, int64_t sink_stride = 0) {
     SCINT_REQUIRE(R >= 1 && C >= 1 && nvalid >= 0 && nvalid <= R, "fft2: bad shape");
     SCINT_REQUIRE(R < (1 << 24) && C < (1 << 24), "fft2: axis longer than 2^24");
-    const Fft2Plan p = make_plan(R, C, nvalid);
+    SCINT_REQUIRE(stack >= 0 && stack <= 65535, "fft2: a stack holds at most 65535 problems");      // (grid.z of the column passes)
+    const int64_t B = stack > 0 ? stack : 1, npairs = (nvalid + 1) / 2;
+    SCINT_REQUIRE(B * std::max(R, nvalid) < (1 << 30), "fft2: too many rows in the stack");
+    const Fft2Plan p = make_plan(R, C, nvalid, B);
+    const int64_t mid_stride = stack ? p.mR * C : 0;       // a problem's column working array
     if (workspace_bytes < p.total) { set_error("scint: fft workspace too small"); return SCINT_E_WORKSPACE; }
     char* base = (char*)workspace;
     cplx* rowA = (cplx*)(base + p.off_rowA);
@@ -778,15 +907,23 @@ static int32_t fft2_general(RowSource src, int64_t nvalid, double fill0, int64_t
         const int ChL = (int)((Ch + 7) & ~(int64_t)7);
         src.n_in = (int)C;
         src.chirp = nullptr;
-        rc = with_source(src, [&](auto s) {
-            return launch_fft_rows(C, (nvalid + 1) / 2, PairLoad<decltype(s)>{s, (int)nvalid},
-                                   PairStore{rowA, ChL, (int)nvalid}, stream);
-        });
+        if (stack)
+            rc = launch_fft_rows(C, B * npairs, StackPairLoad<RowSource>{src, (int)nvalid, (int)npairs},
+                                 StackPairStore{rowA, ChL, (int)nvalid, (int)npairs}, stream);
+        else
+            rc = with_source(src, [&](auto s) {
+                return launch_fft_rows(C, (nvalid + 1) / 2, PairLoad<decltype(s)>{s, (int)nvalid},
+                                       PairStore{rowA, ChL, (int)nvalid}, stream);
+            });
         if (rc != SCINT_OK) return rc;
         ColSourcePlain hs{rowA, ChL, (int)nvalid, fill0};
         sink.R = (int)R; sink.C = (int)C; sink.col_post_w = nullptr; sink.col_post_scale = 1.0; sink.half = 1;
-        ArrayLoad mid_ld{colA, ChL, 0};
-        ArrayStore mid_st{colA, ChL, 0};
+        ArrayLoad mid_ld{colA, ChL, mid_stride};
+        ArrayStore mid_st{colA, ChL, mid_stride};
+        if (stack)
+            return with_stack_sink(sink, sink_stride, [&](auto sk) {
+                return run_cols_fft(R, Ch, B, StackFirst<ColSourcePlain>{hs, nvalid * ChL}, mid_ld, mid_st, sk, stream, 1);
+            });
         return with_sink(sink, [&](auto sk) { return run_cols_fft(R, Ch, 1, hs, mid_ld, mid_st, sk, stream); });
     }
 
@@ -797,14 +934,21 @@ static int32_t fft2_general(RowSource src, int64_t nvalid, double fill0, int64_t
         const int ChL = (int)((Ch + 7) & ~(int64_t)7);
         src.n_in = (int)C;
         src.chirp = nullptr;
-        rc = with_source(src, [&](auto s) {
-            return rows_fft_src(PairRows<decltype(s)>{s, (int)nvalid}, (nvalid + 1) / 2, C, rowA, C, stream);
-        });
+        if (stack)
+            rc = rows_fft_src(StackPairRows<RowSource>{src, (int)nvalid, (int)npairs}, B * npairs, C, rowA, C, stream);
+        else
+            rc = with_source(src, [&](auto s) {
+                return rows_fft_src(PairRows<decltype(s)>{s, (int)nvalid}, (nvalid + 1) / 2, C, rowA, C, stream);
+            });
         if (rc != SCINT_OK) return rc;
         PairSplitSource hs{rowA, (int)C, (int)C, (int)nvalid, fill0};
         sink.R = (int)R; sink.C = (int)C; sink.col_post_w = nullptr; sink.col_post_scale = 1.0; sink.half = 1;
-        ArrayLoad mid_ld{colA, ChL, 0};
-        ArrayStore mid_st{colA, ChL, 0};
+        ArrayLoad mid_ld{colA, ChL, mid_stride};
+        ArrayStore mid_st{colA, ChL, mid_stride};
+        if (stack)
+            return with_stack_sink(sink, sink_stride, [&](auto sk) {
+                return run_cols_fft(R, Ch, B, StackFirst<PairSplitSource>{hs, npairs * C}, mid_ld, mid_st, sk, stream, 1);
+            });
         return with_sink(sink, [&](auto sk) { return run_cols_fft(R, Ch, 1, hs, mid_ld, mid_st, sk, stream); });
     }
 
@@ -814,20 +958,21 @@ static int32_t fft2_general(RowSource src, int64_t nvalid, double fill0, int64_t
     cs.row_post_w = nullptr; cs.row_post_scale = 1.0; cs.chirp = nullptr; cs.mulconj_b = nullptr;
     src.n_in = (int)C;
     src.chirp = nullptr;
+    const int64_t nrows = B * nvalid;          // (the stack's rows are one tall array to the row pass)
     if (!p.blue_c) {
-        rc = rows_fft_pow2(src, nvalid, C, rowA, C, stream);
+        rc = rows_fft_pow2(src, nrows, C, rowA, C, stream);
         if (rc != SCINT_OK) return rc;
         cs.a = rowA; cs.ld = (int)C;
     } else {
         const Chirp* ch = chirp_table(C);
         if (!ch) return SCINT_E_HIP;
         src.chirp = ch->w;
-        rc = rows_fft_pow2(src, nvalid, p.mC, rowA, p.mC, stream);
+        rc = rows_fft_pow2(src, nrows, p.mC, rowA, p.mC, stream);
         if (rc != SCINT_OK) return rc;
         RowSource s2;
         s2.mode = SRC_MULCONJ; s2.n_in = (int)p.mC; s2.chirp = nullptr;
         s2.a = rowA; s2.ld = (int)p.mC; s2.b = ch->B;
-        rc = rows_fft_pow2(s2, nvalid, p.mC, rowB, p.mC, stream);
+        rc = rows_fft_pow2(s2, nrows, p.mC, rowB, p.mC, stream);
         if (rc != SCINT_OK) return rc;
         cs.a = rowB; cs.ld = (int)p.mC;
         cs.row_post_w = ch->w; cs.row_post_scale = 1.0 / (double)p.mC;
@@ -840,23 +985,32 @@ static int32_t fft2_general(RowSource src, int64_t nvalid, double fill0, int64_t
         // a length-1 "FFT": push the row result through the sink with a trivial pass
         SCINT_REQUIRE(false, "fft2: a single-row transform is not supported");
     }
+    const int64_t row_stride = nvalid * cs.ld; // a problem's row-pass result
     if (!p.blue_r) {
-        ArrayLoad mid_ld{colA, (int)C, 0};
-        ArrayStore mid_st{colA, (int)C, 0};
+        ArrayLoad mid_ld{colA, (int)C, mid_stride};
+        ArrayStore mid_st{colA, (int)C, mid_stride};
         if (!p.blue_c) {   // no Bluestein factor anywhere: the plain first loader
             ColSourcePlain ps{cs.a, cs.ld, cs.nvalid, cs.fill0};
+            if (stack)
+                return with_stack_sink(sink, sink_stride, [&](auto sk) {
+                    return run_cols_fft(R, C, B, StackFirst<ColSourcePlain>{ps, row_stride}, mid_ld, mid_st, sk, stream, 1);
+                });
             return with_sink(sink, [&](auto sk) { return run_cols_fft(R, C, 1, ps, mid_ld, mid_st, sk, stream); });
         }
+        if (stack)
+            return run_cols_fft(R, C, B, StackFirst<ColSource>{cs, row_stride}, mid_ld, mid_st, StackSink<>{sink, sink_stride},
+                                stream, 1);
         return run_cols_fft(R, C, 1, cs, mid_ld, mid_st, sink, stream);
     }
     const Chirp* ch = chirp_table(R);
     if (!ch) return SCINT_E_HIP;
     cs.chirp = ch->w;
     {   // pass 1: FFT_mR(x w) -> colB (mids in place in colA)
-        ArrayLoad mid_ld{colA, (int)C, 0};
-        ArrayStore mid_st{colA, (int)C, 0};
-        ArrayStore to_b{colB, (int)C, 0};
-        rc = run_cols_fft(p.mR, C, 1, cs, mid_ld, mid_st, to_b, stream);
+        ArrayLoad mid_ld{colA, (int)C, mid_stride};
+        ArrayStore mid_st{colA, (int)C, mid_stride};
+        ArrayStore to_b{colB, (int)C, mid_stride};
+        if (stack) rc = run_cols_fft(p.mR, C, B, StackFirst<ColSource>{cs, row_stride}, mid_ld, mid_st, to_b, stream, 1);
+        else rc = run_cols_fft(p.mR, C, 1, cs, mid_ld, mid_st, to_b, stream);
         if (rc != SCINT_OK) return rc;
     }
     {   // pass 2: FFT_mR(conj(A B)) -> w[k] conj(.)/mR -> sink  (mids in place in colB... the
@@ -864,14 +1018,22 @@ static int32_t fft2_general(RowSource src, int64_t nvalid, double fill0, int64_t
         ColSource c2;
         c2.a = colB; c2.ld = (int)C; c2.nvalid = (int)p.mR; c2.fill0 = 0.0; c2.n_in = (int)p.mR;
         c2.row_post_w = nullptr; c2.row_post_scale = 1.0; c2.chirp = nullptr; c2.mulconj_b = ch->B;
-        ArrayLoad mid_ld{colA, (int)C, 0};
-        ArrayStore mid_st{colA, (int)C, 0};
+        ArrayLoad mid_ld{colA, (int)C, mid_stride};
+        ArrayStore mid_st{colA, (int)C, mid_stride};
         sink.col_post_w = ch->w; sink.col_post_scale = 1.0 / (double)p.mR;
+        if (stack)
+            return run_cols_fft(p.mR, C, B, StackFirst<ColSource>{c2, mid_stride}, mid_ld, mid_st, StackSink<>{sink, sink_stride},
+                                stream, 1);
         return run_cols_fft(p.mR, C, 1, c2, mid_ld, mid_st, sink, stream);
     }
 }
 
-static size_t fft2_general_ws(int64_t R, int64_t C, int64_t nvalid) { return make_plan(R, C, nvalid).total; }
+// A stack whose problems are beyond the cache takes the tiled column passes (run_cols_fft), which number their tile slots in 32 bits:
+// the limit an entry point for stacks checks with its shape, so that it is an argument error there and not deep inside the call.
+static bool stack_cols_ok(int64_t B, int64_t R, int64_t C) {
+    return (double)R * (double)C * 16.0 <= 300.0 * 1048576.0 || B * ceil_div(C, 16) * 128 < ((int64_t)1 << 32);
+}
+static size_t fft2_general_ws(int64_t R, int64_t C, int64_t nvalid, int64_t B = 1) { return make_plan(R, C, nvalid, B).total; }
 
 // ------------------------------------------------------------------------------
 // model = real(ifft2(ifftshift(recov)))  (ththmod.py:316-317, 357-358) as a complex-to-real transform
@@ -1086,7 +1248,7 @@ extern "C" int32_t scint_sspec(const double* dyn, int64_t nf, int64_t nt, const 
     double* scal = cv.take<double>(8);  // [0] = mean1, [1] = mean2
 
     {
-        const int blocks = (int)std::min<int64_t>(kRedBlocks, nf);
+        const int blocks = sspec_sums_blocks(nf);
         hipLaunchKernelGGL(sspec_sums_kernel, dim3(blocks), dim3(256), 0, stream, dyn, win_t, win_f, nf, nt, partial);
         hipLaunchKernelGGL(sspec_means_kernel, dim3(1), dim3(256), 0, stream, partial, blocks, (double)(nf * nt), scal);
         SCINT_LAUNCH_CHECK();
@@ -1099,6 +1261,74 @@ extern "C" int32_t scint_sspec(const double* dyn, int64_t nf, int64_t nt, const 
     sink.mode = SINK_SSPEC; sink.out_d = sec_out; sink.halve = halve; sink.prewhite = prewhite;
     sink.pd_fd = pd_fd; sink.pd_td = pd_td;
     return fft2_general(src, nf_eff, 0.0, R, C, sink, workspace, fft_bytes, stream, /*real_input=*/true);
+}
+
+// ------------------------------------------------------------------------------
+// scint_sspec_batch: scint_sspec of every problem of a stack [B][nf][nt]
+// ------------------------------------------------------------------------------
+// Segments whose padded half-lengths are below 256 on either axis (up to 128 channels or 128 sub-integrations) -- the ones a cut
+// into many segments makes -- take scint_sspec's fft2_general route as a stack: the two means per problem (2 launches, grid.y),
+// the row pass over the stacked rows, the column passes with the problem as grid.z; launches do not grow with B.  Larger ones
+// take scint_sspec's persistent kernels (sspec.hip), which have no problem index: they run problem after problem on one
+// problem's workspace, so their launches DO grow with B (a cut leaves few segments of that size).  Either way out[b] has the
+// bits of scint_sspec on stack[b].
+namespace scint {
+static bool sspec_batch_shape_ok(int64_t B, int64_t nf, int64_t nt) {
+    return B >= 1 && B <= 65535 && nf >= 2 && nt >= 2 && nf < (1 << 22) && nt < (1 << 22) && B * 2 * next_pow2(nf) < (1 << 30) &&
+           stack_cols_ok(B, 2 * next_pow2(nf), 2 * next_pow2(nt));
+}
+}  // namespace scint
+
+extern "C" int32_t scint_sspec_batch_workspace_bytes(int64_t B, int64_t nf, int64_t nt, int32_t halve, size_t* bytes) {
+    SCINT_REQUIRE(bytes != nullptr, "sspec_batch_workspace_bytes: null output");
+    SCINT_REQUIRE(sspec_batch_shape_ok(B, nf, nt), "sspec_batch_workspace_bytes: bad shape (1 <= B <= 65535, nf >= 2, nt >= 2)");
+    if (sspec_fast_supported(nf, nt, halve)) return scint_sspec_workspace_bytes(nf, nt, bytes);
+    const int64_t R = 2 * next_pow2(nf), C = std::max<int64_t>(16, 2 * next_pow2(nt));
+    *bytes = align_up(fft2_general_ws(R, C, nf, B), 256) +
+             align_up(sizeof(double) * 3 * (size_t)B * (size_t)sspec_sums_blocks(nf), 256) + align_up(sizeof(double) * 2 * (size_t)B, 256);
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_sspec_batch(const double* stack, int64_t B, int64_t nf, int64_t nt, const double* win_t,
+                                     const double* win_f, int32_t prewhite, int32_t halve, const double* pd_fd,
+                                     const double* pd_td, double* sec_out, void* workspace, size_t workspace_bytes, void* stream_) {
+    SCINT_REQUIRE(stack && sec_out && workspace, "sspec_batch: null pointer");
+    SCINT_REQUIRE(sspec_batch_shape_ok(B, nf, nt), "sspec_batch: bad shape (1 <= B <= 65535, nf >= 2, nt >= 2)");
+    SCINT_REQUIRE((win_t == nullptr) == (win_f == nullptr), "sspec_batch: give both windows or neither");
+    SCINT_REQUIRE(!prewhite || halve, "sspec_batch: cannot apply prewhite to full frame");
+    SCINT_REQUIRE(!prewhite || (pd_fd && pd_td), "sspec_batch: prewhite needs post-darkening vectors");
+    hipStream_t stream = (hipStream_t)stream_;
+    size_t need = 0;
+    scint_sspec_batch_workspace_bytes(B, nf, nt, halve, &need);
+    if (workspace_bytes < need) { set_error("scint: sspec_batch workspace too small"); return SCINT_E_WORKSPACE; }
+    const int64_t R = 2 * next_pow2(nf), C = 2 * next_pow2(nt);
+    SCINT_REQUIRE(C >= 16, "sspec_batch: nt must be at least 5");
+    const int64_t out_stride = (halve ? R / 2 : R) * C;
+    if (sspec_fast_supported(nf, nt, halve)) {
+        for (int64_t b = 0; b < B; ++b) {
+            const int32_t rc = sspec_fast(stack + b * nf * nt, nf, nt, win_t, win_f, prewhite, pd_fd, pd_td, sec_out + b * out_stride,
+                                          workspace, stream);
+            if (rc != SCINT_OK) return rc;
+        }
+        return SCINT_OK;
+    }
+    const size_t fft_bytes = align_up(fft2_general_ws(R, C, nf, B), 256);
+    Carver cv((char*)workspace + fft_bytes, workspace_bytes - fft_bytes);
+    const int blocks = sspec_sums_blocks(nf);
+    double* partial = cv.take<double>(3 * (size_t)B * (size_t)blocks);
+    double* scal = cv.take<double>(2 * (size_t)B);   // [2 b] = mean1, [2 b + 1] = mean2 of problem b
+    hipLaunchKernelGGL(sspec_stack_sums_kernel, dim3(blocks, (unsigned)B), dim3(256), 0, stream, stack, win_t, win_f, nf, nt, partial);
+    hipLaunchKernelGGL(sspec_stack_means_kernel, dim3(1, (unsigned)B), dim3(256), 0, stream, (const double*)partial, blocks,
+                       (double)(nf * nt), scal);
+    SCINT_LAUNCH_CHECK();
+    const int64_t nf_eff = prewhite ? nf - 1 : nf, nt_eff = prewhite ? nt - 1 : nt;
+    RowSource src{};
+    src.mode = SRC_SSPEC_STACK; src.wv = WindowedValue{stack, win_t, win_f, scal, (int)nt};
+    src.nt_eff = nt_eff; src.prewhite = prewhite; src.prob_rows = (int)nf_eff; src.prob_src_rows = (int)nf;
+    ColSink sink{};
+    sink.mode = SINK_SSPEC; sink.out_d = sec_out; sink.halve = halve; sink.prewhite = prewhite;
+    sink.pd_fd = pd_fd; sink.pd_td = pd_td;
+    return fft2_general(src, nf_eff, 0.0, R, C, sink, workspace, fft_bytes, stream, /*real_input=*/true, B, out_stride);
 }
 
 // ------------------------------------------------------------------------------
@@ -1266,8 +1496,7 @@ namespace scint {
 struct MaxAbsValue {   // arr /= np.max(arr): the maximum of a real array via two-stage max
     const double* x;
 };
-__global__ void __launch_bounds__(256) max_partial_kernel(const double* x, int64_t n, double* partial) {
-    __shared__ double red[4];
+__device__ inline void max_partial_body(const double* x, int64_t n, double* partial, double* red) {
     double m = -INFINITY;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         m = fmax(m, x[i]);
@@ -1276,13 +1505,38 @@ __global__ void __launch_bounds__(256) max_partial_kernel(const double* x, int64
     __syncthreads();
     if (threadIdx.x == 0) partial[blockIdx.x] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
 }
-__global__ void __launch_bounds__(256) scale_by_max_kernel(double* x, int64_t n, const double* partial, int np) {
+__global__ void __launch_bounds__(256) max_partial_kernel(const double* x, int64_t n, double* partial) {
+    __shared__ double red[4];
+    max_partial_body(x, n, partial, red);
+}
+__device__ inline void scale_by_max_body(double* x, int64_t n, const double* partial, int np) {
     double m = -INFINITY;
     for (int i = 0; i < np; ++i) m = fmax(m, partial[i]);
     const double inv = 1.0 / m;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         x[i] = x[i] / m;
     (void)inv;
+}
+__global__ void __launch_bounds__(256) scale_by_max_kernel(double* x, int64_t n, const double* partial, int np) {
+    scale_by_max_body(x, n, partial, np);
+}
+
+// The reductions of a stack x[B][n]: problem blockIdx.y runs the single problem's body with the single problem's grid.x on its own
+// values, partials (gridDim.x of them) and result -- its mean and its maximum have the bits of the call that takes it alone.
+__global__ void __launch_bounds__(256) stack_sum_partial_kernel(const double* x, int64_t n, double* partial) {
+    __shared__ double red[4];
+    reduce_partial_body(PlainValue{x + (int64_t)blockIdx.y * n}, n, partial + (int64_t)blockIdx.y * gridDim.x, red);
+}
+__global__ void __launch_bounds__(256) stack_sum_final_kernel(const double* partial, int np, double scale, double* out) {
+    __shared__ double red[4];
+    reduce_final_body(partial + (int64_t)blockIdx.y * np, np, scale, out + blockIdx.y, red);
+}
+__global__ void __launch_bounds__(256) stack_max_partial_kernel(const double* x, int64_t n, double* partial) {
+    __shared__ double red[4];
+    max_partial_body(x + (int64_t)blockIdx.y * n, n, partial + (int64_t)blockIdx.y * gridDim.x, red);
+}
+__global__ void __launch_bounds__(256) stack_scale_by_max_kernel(double* x, int64_t n, const double* partial, int np) {
+    scale_by_max_body(x + (int64_t)blockIdx.y * n, n, partial + (int64_t)blockIdx.y * np, np);
 }
 }  // namespace scint
 
@@ -1326,9 +1580,77 @@ extern "C" int32_t scint_acf(const double* dyn, int64_t nf, int64_t nt, int32_t 
     // the power spectrum is real and even, so fft2 and ifft2 of it coincide up to the 1/(RC) factor
     rc = fft2_general(b, R, 0.0, R, C, bs, workspace, fft_bytes, stream, /*real_input=*/true);
     if (rc != SCINT_OK || !normalise) return rc;
-    const int blocks = (int)std::min<int64_t>(kRedBlocks, std::max<int64_t>(1, ceil_div(R * C, 1024)));
+    const int blocks = max_blocks(R * C);
     hipLaunchKernelGGL(max_partial_kernel, dim3(blocks), dim3(256), 0, stream, acf_out, R * C, partial);
     hipLaunchKernelGGL(scale_by_max_kernel, dim3(blocks), dim3(256), 0, stream, acf_out, R * C, partial, blocks);
+    SCINT_LAUNCH_CHECK();
+    return SCINT_OK;
+}
+
+// ------------------------------------------------------------------------------
+// scint_acf_batch: scint_acf of every problem of a stack [B][nf][nt] in launches that do not grow with B
+// ------------------------------------------------------------------------------
+// Per group of B problems: the means (2 launches, or a memset), the forward transform, the transform of the power, the maxima
+// and the division (2 launches) -- fft2_general's row and column passes with the problem as a range of slots / grid.z.
+// Moved per problem: 8 nf nt read; the complex intermediates (the row pass's result and the column working array of both
+// transforms, and the spectrum between them) written and read once each, 16 * 2nf * 2nt bytes apiece at power-of-two
+// lengths; 8 * 4 nf nt written, and read and written once more by the normalisation.
+namespace scint {
+static bool acf_batch_shape_ok(int64_t B, int64_t nf, int64_t nt) {
+    return B >= 1 && B <= 65535 && nf >= 1 && nt >= 1 && nf < (1 << 23) && nt < (1 << 23) && B * 2 * nf < (1 << 30) &&
+           (double)B * (double)nf * (double)nt < 1e15 && stack_cols_ok(B, 2 * nf, 2 * nt);
+}
+}  // namespace scint
+
+extern "C" int32_t scint_acf_batch_workspace_bytes(int64_t B, int64_t nf, int64_t nt, size_t* bytes) {
+    SCINT_REQUIRE(bytes != nullptr, "acf_batch_workspace_bytes: null output");
+    SCINT_REQUIRE(acf_batch_shape_ok(B, nf, nt), "acf_batch_workspace_bytes: bad shape (1 <= B <= 65535, nf >= 1, nt >= 1)");
+    const int64_t R = 2 * nf, C = 2 * nt;
+    *bytes = align_up(fft2_general_ws(R, C, R, B), 256) + align_up(sizeof(cplx) * (size_t)B * (size_t)R * (size_t)C, 256) +
+             align_up(sizeof(double) * (size_t)B * (size_t)max_blocks(R * C), 256) + align_up(sizeof(double) * (size_t)B, 256);
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_acf_batch(const double* stack, int64_t B, int64_t nf, int64_t nt, int32_t subtract_mean,
+                                   int32_t normalise, double* acf_out, void* workspace, size_t workspace_bytes, void* stream_) {
+    SCINT_REQUIRE(stack && acf_out && workspace, "acf_batch: null pointer");
+    SCINT_REQUIRE(acf_batch_shape_ok(B, nf, nt), "acf_batch: bad shape (1 <= B <= 65535, nf >= 1, nt >= 1)");
+    size_t need = 0;
+    scint_acf_batch_workspace_bytes(B, nf, nt, &need);
+    if (workspace_bytes < need) { set_error("scint: acf_batch workspace too small"); return SCINT_E_WORKSPACE; }
+    hipStream_t stream = (hipStream_t)stream_;
+    const int64_t R = 2 * nf, C = 2 * nt;
+    const size_t fft_bytes = align_up(fft2_general_ws(R, C, R, B), 256);
+    Carver cv((char*)workspace + fft_bytes, workspace_bytes - fft_bytes);
+    cplx* spec = cv.take<cplx>((size_t)B * (size_t)R * (size_t)C);
+    double* partial = cv.take<double>((size_t)B * (size_t)max_blocks(R * C));      // (>= the mean's: R C = 4 nf nt)
+    double* scal = cv.take<double>((size_t)B);
+    if (subtract_mean) {
+        const int blocks = reduce_blocks(nf * nt);
+        hipLaunchKernelGGL(stack_sum_partial_kernel, dim3(blocks, (unsigned)B), dim3(256), 0, stream, stack, nf * nt, partial);
+        hipLaunchKernelGGL(stack_sum_final_kernel, dim3(1, (unsigned)B), dim3(256), 0, stream, (const double*)partial, blocks,
+                           1.0 / (double)(nf * nt), scal);
+        SCINT_LAUNCH_CHECK();
+    } else {
+        SCINT_HIP(hipMemsetAsync(scal, 0, sizeof(double) * (size_t)B, stream));
+    }
+    RowSource f{};
+    f.mode = SRC_ACF_IN; f.wv.dyn = stack; f.wv.nt = nt; f.wv.m1 = scal; f.prob_rows = (int)nf;
+    ColSink fs{};
+    fs.mode = SINK_ARRAY; fs.out_c = spec; fs.ld = C;
+    int32_t rc = fft2_general(f, nf, 0.0, R, C, fs, workspace, fft_bytes, stream, /*real_input=*/true, B, R * C);
+    if (rc != SCINT_OK) return rc;
+    RowSource b{};
+    b.mode = SRC_POWER; b.a = spec; b.ld = C;
+    ColSink bs{};
+    bs.mode = SINK_ACF; bs.out_d = acf_out; bs.scale = 1.0 / ((double)R * (double)C);
+    rc = fft2_general(b, R, 0.0, R, C, bs, workspace, fft_bytes, stream, /*real_input=*/true, B, R * C);
+    if (rc != SCINT_OK || !normalise) return rc;
+    const int blocks = max_blocks(R * C);
+    hipLaunchKernelGGL(stack_max_partial_kernel, dim3(blocks, (unsigned)B), dim3(256), 0, stream, (const double*)acf_out, R * C,
+                       partial);
+    hipLaunchKernelGGL(stack_scale_by_max_kernel, dim3(blocks, (unsigned)B), dim3(256), 0, stream, acf_out, R * C,
+                       (const double*)partial, blocks);
     SCINT_LAUNCH_CHECK();
     return SCINT_OK;
 }
@@ -1360,7 +1682,7 @@ extern "C" int32_t scint_acf_sspec(const double* sec_db, int64_t R, int64_t C, i
     fs.mode = SINK_ACF; fs.out_d = acf_out; fs.scale = 1.0;      // real(fftshift(fft2(.)))
     int32_t rc = fft2_general(f, R, 0.0, R, C, fs, workspace, fft_bytes, stream, /*real_input=*/true);
     if (rc != SCINT_OK || !normalise) return rc;
-    const int blocks = (int)std::min<int64_t>(kRedBlocks, std::max<int64_t>(1, ceil_div(R * C, 1024)));
+    const int blocks = max_blocks(R * C);
     hipLaunchKernelGGL(max_partial_kernel, dim3(blocks), dim3(256), 0, stream, acf_out, R * C, partial);
     hipLaunchKernelGGL(scale_by_max_kernel, dim3(blocks), dim3(256), 0, stream, acf_out, R * C, partial, blocks);
     SCINT_LAUNCH_CHECK();

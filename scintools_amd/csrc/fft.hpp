@@ -623,9 +623,11 @@ struct ColsBStore {
 // Runs a strided-axis FFT.  `first` loads the source, `mid_ld/mid_st` are the plain in-place
 // accessors of the working array, `last` stores the final (natural-order) result.
 // Lengths >= 256: two tiled passes (above); shorter ones: radix passes of fft_cols_kernel.
+// `route_batches` > 0: choose between the two as for that many batches -- a stack of independent problems passes 1, so that
+// every problem takes the passes (and gets the bits) of the call that transforms it alone.
 template <class FirstLoader, class MidLoader, class MidStorer, class LastStorer>
 int32_t run_cols_fft(int64_t len, int64_t ncols, int64_t batches, FirstLoader first,
-                     MidLoader mid_ld, MidStorer mid_st, LastStorer last, hipStream_t stream) {
+                     MidLoader mid_ld, MidStorer mid_st, LastStorer last, hipStream_t stream, int64_t route_batches = 0) {
     SCINT_REQUIRE(is_pow2(len) && len >= 2, "fft cols: length must be a power of two >= 2");
     SCINT_REQUIRE(len <= (1 << 24) && ncols < (1 << 30), "fft cols: extent beyond the 32-bit index range");
     const cplx* tw = twiddle_table(len);
@@ -634,7 +636,8 @@ int32_t run_cols_fft(int64_t len, int64_t ncols, int64_t batches, FirstLoader fi
     // passes re-read what they just wrote from the cache and win (4096^2 complex: 0.23 vs 0.28 ms);
     // beyond it every radix pass is an HBM round trip and the two tiled passes win (16384^2: 5.6
     // vs 7.3 ms).
-    const bool beyond_cache = (double)len * (double)ncols * (double)batches * 16.0 > 300.0 * 1048576.0;
+    const bool beyond_cache =
+        (double)len * (double)ncols * (double)(route_batches > 0 ? route_batches : batches) * 16.0 > 300.0 * 1048576.0;
     if (beyond_cache && len >= 256 && len <= 16384) {
         const int l = ilog2(len), l2 = l / 2, l1 = l - l2;          // L1 >= L2, both in [16, 128]
         const int64_t ntiles = ceil_div(ncols, 16);

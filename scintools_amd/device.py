@@ -130,6 +130,11 @@ class DeviceBacked:
     def present(self, obj):
         return obj.__dict__.get(self.slot) is not None
 
+    def on_device(self, obj):
+        """True while the value is parked in HBM and no host read has copied it down yet."""
+        state = obj.__dict__.get(self.slot)
+        return state is not None and state[0] is None and state[1] is not None
+
     def tensor(self, obj, dtype=torch.float64):
         """Device tensor of the current value: the parked one, or an upload of the host array."""
         state = obj.__dict__.get(self.slot)

@@ -112,6 +112,37 @@ def sspec_device(dyn_t, prewhite=False, halve=True, window="hanning", window_fra
     return out
 
 
+def sspec_stack_device(stack_t, prewhite=False, halve=True, window="hanning", window_frac=0.1, out=None, group_bytes=None):
+    """``sspec_device`` of every dynamic spectrum of a contiguous device stack [B, nf, nt] float64 -> device tensor [B, rows, ncfft],
+    problem for problem the bits of ``sspec_device(stack_t[k], prewhite, halve, window, window_frac)`` (``scint_sspec_batch``).  The
+    window and post-darkening tables are built once per call.  Segments of up to 128 channels or 128 sub-integrations go through
+    the single call's kernels as slots and grid.z, in launches that do not grow with B; the stack is then taken in groups whose
+    workspace stays below ``group_bytes`` (None: ``scintpar.STACK_GROUP_BYTES``).  Larger segments run the single call's persistent
+    kernels problem after problem inside the one library call.  ``out``: a contiguous device tensor of the result's shape."""
+    import ctypes
+    require_gpu()
+    B, nf, nt = scintpar._check_stack("sspec_stack_device", stack_t)
+    nrfft = int(2 ** (np.ceil(np.log2(nf)) + 1))      # dynspec.py:3677
+    ncfft = int(2 ** (np.ceil(np.log2(nt)) + 1))      # dynspec.py:3678
+    if prewhite and not halve:
+        raise RuntimeError("Cannot apply prewhite to full frame")   # dynspec.py:3717
+    wt, wf = _window_tables(nt, nf, window, window_frac, torch.cuda.current_device())
+    pd_fd, pd_td = _postdark_tables(nrfft, ncfft, torch.cuda.current_device()) if prewhite else (None, None)
+    shape = (B, nrfft // 2 if halve else nrfft, ncfft)
+    if out is None:
+        out = empty(shape, torch.float64)
+    elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError(f"sspec_stack_device: out must be a contiguous float64 tensor of shape {shape}")
+    hv = 1 if halve else 0
+    one = ctypes.c_size_t()
+    _lib.call("scint_sspec_batch_workspace_bytes", 1, nf, nt, hv, one)
+    for b0, n in scintpar._stack_groups(B, one.value, group_bytes):
+        ws = workspace_for("scint_sspec_batch", n, nf, nt, hv)
+        _lib.call("scint_sspec_batch", stack_t[b0:b0 + n], n, nf, nt, wt, wf, 1 if prewhite else 0, hv, pd_fd, pd_td,
+                  out[b0:b0 + n], ws, ws.numel(), stream_ptr())
+    return out
+
+
 class Dynspec:
     """Dynamic-spectrum holder with the reference's attribute names
     (dynspec.py:400-413) and a GPU ``calc_sspec``.
@@ -132,6 +163,9 @@ class Dynspec:
     trapsspec = DeviceBacked("trapsspec")
     acf_model = DeviceBacked("acf_model")    # the fitted approximate 2-D model over the fit's window (fit_scint_params_2d)
     acf =DeviceBacked("acf")                # [2 nf, 2 nt]: 512 MB for a 4096^2 observation; the scales read a few cuts of it
+    cutdyn = DeviceBacked("cutdyn")          # cut_dyn's three stacks (0.94 GB for a 4096^2 observation): a caller who reads one
+    cutsspec = DeviceBacked("cutsspec")      # of them downloads that one
+    cutacf = DeviceBacked("cutacf")
 
     def __init__(self, filename=None, dyn=None, verbose=True, process=False, lamsteps=False,
                  remove_short_subs=True, subint_thresh=2.33, mjd=None):

@@ -10,9 +10,11 @@ The functions are bound onto ``scintools_amd.dynspec.Dynspec`` as ``arcfit``'s a
 * ``get_acf_tilt``: per selected ACF row the first column of the maximum and the 7 samples around it come from the device
   (``scint_acf_row_peaks``); ``fit_parabola`` per row and the weighted ``np.polyfit`` run on the host.  A row whose 7-sample
   window would cross the first or last column raises ``ValueError`` (the reference's slice is empty, or short, there).
-* ``cut_dyn``: one upload of ``dyn``; segments cut on the device (``scint_segment_cut``), every segment's secondary spectrum and
-  ACF from device memory, each output stack downloaded once.  ``self.cutacf`` is the one addition: the reference computes every
-  segment's ACF and discards it.
+* ``cut_dyn``: one upload of ``dyn``; segments cut on the device (``scint_segment_cut``), every segment's secondary spectrum
+  (``dynspec.sspec_stack_device``, ``scint_sspec_batch``) and ACF (``acf_stack_device``, ``scint_acf_batch``) from one batched call
+  each, from device memory; the
+  three stacks stay in HBM until they are read (``device.DeviceBacked``).  ``self.cutacf`` is the one addition: the reference
+  computes every segment's ACF and discards it.
 
 The fitted methods of ``get_scint_params`` (``acf1d``, ``acf2d_approx``, ``acf2d``, ``sspec``, ``mcmc``) need lmfit and raise
 ``NotImplementedError``.  The 1-D ACF fit itself -- the reference's default, dynspec.py:2650-2702 with scint_models.py:62-120 -- runs
@@ -26,6 +28,7 @@ So does the approximate 2-D fit (``method='acf2d_approx'``, dynspec.py:2689-2842
 the phase gradient: ``acf2d_approx_fit_device`` (one workgroup per problem, ``scint_acf2d_approx_fit``, csrc/acf2d.hpp),
 ``fit_scint_params_2d`` and ``fit_scint_params_2d_cut``.
 """
+import ctypes
 import warnings
 
 import numpy as np
@@ -63,6 +66,51 @@ def acf_device(dyn_t, subtract_mean=True, normalise=True, out=None):
         out = device.empty((2 * nf, 2 * nt), torch.float64)
     _lib.call("scint_acf", dyn_t, nf, nt, 1 if subtract_mean else 0, 1 if normalise else 0, out, ws, ws.numel(),
               device.stream_ptr())
+    return out
+
+
+STACK_GROUP_BYTES = 8 << 30     # workspace a group of a stack's problems may hold at once (ththmod.RETRIEVAL_GROUP_BYTES)
+STACK_GROUP_MAX = 65535         # problems of one call: grid.z of the column passes (csrc/fft.hip)
+
+
+def _stack_groups(B, bytes_per_problem, group_bytes):
+    """``(start, count)`` of the groups a stack of B problems is taken in: as many problems as fit into ``group_bytes`` (None or 0:
+    STACK_GROUP_BYTES), at least one, at most STACK_GROUP_MAX -- ``ththmod._group_size``'s rule."""
+    per = min(STACK_GROUP_MAX, max(1, int((group_bytes or STACK_GROUP_BYTES) // bytes_per_problem)))
+    return [(b0, min(per, B - b0)) for b0 in range(0, B, per)]
+
+
+def _check_stack(what, stack_t):
+    if not torch.is_tensor(stack_t) or stack_t.dim() != 3:
+        raise ValueError(f"{what}: expected a stack of dynamic spectra [B, nf, nt]")
+    if stack_t.dtype != torch.float64:
+        raise ValueError(f"{what}: expected a float64 stack, got {stack_t.dtype}")
+    if not stack_t.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous stack")
+    if stack_t.shape[0] < 1:
+        raise ValueError(f"{what}: the stack is empty")
+    return (int(v) for v in stack_t.shape)
+
+
+def acf_stack_device(stack_t, subtract_mean=False, normalise=True, out=None, group_bytes=None):
+    """``acf_device`` of every dynamic spectrum of a contiguous device stack [B, nf, nt] float64 -> device tensor [B, 2 nf, 2 nt],
+    problem for problem the bits of ``acf_device(stack_t[k], subtract_mean, normalise)`` (``scint_acf_batch``: the problems are
+    slots and grid.z of the single call's kernels, so the launches do not grow with B).  The workspace does: the stack is taken in
+    groups whose workspace stays below ``group_bytes`` (None: STACK_GROUP_BYTES), a handful of launches per group.  ``out``: a
+    contiguous device tensor of the result's shape to write into.  (``subtract_mean`` defaults to ``cut_dyn``'s: none.)"""
+    _lib_ready()
+    B, nf, nt = _check_stack("acf_stack_device", stack_t)
+    shape = (B, 2 * nf, 2 * nt)
+    if out is None:
+        out = device.empty(shape, torch.float64)
+    elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError(f"acf_stack_device: out must be a contiguous float64 tensor of shape {shape}")
+    one = ctypes.c_size_t()
+    _lib.call("scint_acf_batch_workspace_bytes", 1, nf, nt, one)
+    for b0, n in _stack_groups(B, one.value, group_bytes):
+        ws = device.workspace_for("scint_acf_batch", n, nf, nt)      # (no more than n times one problem's)
+        _lib.call("scint_acf_batch", stack_t[b0:b0 + n], n, nf, nt, 1 if subtract_mean else 0, 1 if normalise else 0,
+                  out[b0:b0 + n], ws, ws.numel(), device.stream_ptr())
     return out
 
 
@@ -341,10 +389,10 @@ def cut_dyn(self, tcuts=0, fcuts=0, plot=False, filename=None, dpi=200, lamsteps
     ncfft]`` as the reference does (floor division, remainders dropped; ``lamsteps`` only changes the y-axis of a segment's
     spectrum in the reference, not its data, so it changes nothing here) and -- the one addition -- ``cutacf [.., 2 fnum,
     2 tnum]``, which the reference computes and discards.  ``dyn`` is uploaded once, the segments never visit the host, each
-    stack is downloaded once."""
+    stack stays in HBM until it is first read (``device.DeviceBacked``)."""
     if plot:
         raise NotImplementedError("plotting is outside the accelerated path")
-    from .dynspec import sspec_device
+    from .dynspec import sspec_stack_device
     _lib_ready()
     nchan = len(self.freqs)  # re-define in case of trimming
     nsub = len(self.times)
@@ -362,14 +410,12 @@ def cut_dyn(self, tcuts=0, fcuts=0, plot=False, filename=None, dpi=200, lamsteps
     ncfft = int(2**(np.ceil(np.log2(int(tnum)))+1))
     nseg = (fcuts + 1) * (tcuts + 1)
     segs = segment_cut_device(device.to_device(dyn, torch.float64), fnum, tnum, fcuts + 1, tcuts + 1)
-    sspecs = device.empty((nseg, nrfft, ncfft), torch.float64)
-    acfs = device.empty((nseg, 2 * fnum, 2 * tnum), torch.float64)
-    for k in range(nseg):
-        sspec_device(segs[k], out=sspecs[k])
-        acf_device(segs[k], subtract_mean=False, out=acfs[k])     # (with input_dyn the reference subtracts no mean)
-    self.cutdyn = segs.cpu().numpy().reshape(fcuts + 1, tcuts + 1, fnum, tnum)
-    self.cutsspec = sspecs.cpu().numpy().reshape(fcuts + 1, tcuts + 1, nrfft, ncfft)
-    self.cutacf = acfs.cpu().numpy().reshape(fcuts + 1, tcuts + 1, 2 * fnum, 2 * tnum)
+    sspecs = sspec_stack_device(segs)
+    acfs = acf_stack_device(segs, subtract_mean=False)            # (with input_dyn the reference subtracts no mean)
+    cls = type(self)
+    cls.cutdyn.park(self, segs.view(fcuts + 1, tcuts + 1, fnum, tnum))
+    cls.cutsspec.park(self, sspecs.view(fcuts + 1, tcuts + 1, nrfft, ncfft))
+    cls.cutacf.park(self, acfs.view(fcuts + 1, tcuts + 1, 2 * fnum, 2 * tnum))
 
 
 def fit_scint_params(self, alpha=5/3, full_frame=False, nscale=5, weighted=True, bartlett=True, verbose=False):
@@ -443,9 +489,7 @@ def fit_scint_params_cut(self, tcuts=0, fcuts=0, alpha=5/3, full_frame=False, ns
         raise ValueError("fit_scint_params_cut on the GPU needs a finite dynamic spectrum (run refill first)")
     nseg = (fcuts + 1) * (tcuts + 1)
     segs = segment_cut_device(device.to_device(dyn, torch.float64), fnum, tnum, fcuts + 1, tcuts + 1)
-    acfs = device.empty((nseg, 2 * fnum, 2 * tnum), torch.float64)
-    for k in range(nseg):
-        acf_device(segs[k], subtract_mean=False, out=acfs[k])
+    acfs = acf_stack_device(segs, subtract_mean=False)
     fit = acf1d_fit_device(acfs, self.dt, self.df, fnum * self.df, tnum * self.dt, alpha=alpha, nscale=nscale,
                            full_frame=full_frame, weighted=weighted, bartlett=bartlett)
     shape = (fcuts + 1, tcuts + 1)
@@ -710,9 +754,7 @@ def fit_scint_params_2d_cut(self, tcuts=0, fcuts=0, alpha=5/3, full_frame=False,
         raise ValueError("fit_scint_params_2d_cut on the GPU needs a finite dynamic spectrum (run refill first)")
     nseg = (fcuts + 1) * (tcuts + 1)
     segs = segment_cut_device(device.to_device(dyn, torch.float64), fnum, tnum, fcuts + 1, tcuts + 1)
-    acfs = device.empty((nseg, 2 * fnum, 2 * tnum), torch.float64)
-    for k in range(nseg):
-        acf_device(segs[k], subtract_mean=False, out=acfs[k])
+    acfs = acf_stack_device(segs, subtract_mean=False)
     fit = acf2d_approx_fit_device(acfs, self.dt, self.df, fnum * self.df, tnum * self.dt, nsub=tnum, nchan=fnum, alpha=alpha,
                                   nscale=nscale, full_frame=full_frame, weighted=weighted, bartlett=bartlett,
                                   tau_vary_2d=tau_vary_2d)
