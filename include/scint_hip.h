@@ -57,7 +57,8 @@ extern "C" {
  *   108: scint_two_curve_map / scint_sv_sweep_multi (the thin-screen search, scint_thin_geom);
  *   (the VLBI entry points -- scint_cs_complex_batch / scint_vlbi_composite / scint_eigh_top_batch -- and the batched 1-D ACF fit --
  *   scint_acf1d_fit -- and the approximate 2-D one -- scint_acf2d_approx_fit -- and the biharmonic fill -- scint_inpaint_biharmonic --
- *   and the ACFs and secondary spectra of a stack -- scint_acf_batch, scint_sspec_batch -- only ADD symbols: no bump; a build without them fails at load, which checks every declared symbol) */
+ *   and the ACFs and secondary spectra of a stack -- scint_acf_batch, scint_sspec_batch -- and the arc fits of a stack --
+ *   scint_arc_profile_batch, scint_arc_peak_fit -- only ADD symbols: no bump; a build without them fails at load, which checks every declared symbol) */
 #define SCINT_ABI_VERSION 108
 
 #define SCINT_OK 0
@@ -685,6 +686,52 @@ int32_t scint_row_nanmean(const double* sspec, int64_t ld, int64_t nc, int64_t r
 int32_t scint_block_std(const double* a, int64_t ld, int64_t nc, int64_t r0, int64_t r1,
                         int64_t c_lo, int64_t c_hi, double* out, void* workspace,
                         size_t workspace_bytes, void* stream);
+
+/* ---- arc fits over a stack of spectra (scintools_amd/csrc/arcbatch.hpp) ----------------------------------------------------
+ * scint_arc_profile_batch: for every problem b of sspec[B][R][ld] (dB, nc columns, 1 <= B <= 65535, SCINT_E_ARG otherwise) with
+ * shared fdop[nc] (ascending), yaxis[R], delay rows [row0, row0 + nr) (row0 + nr <= R) and x[nx]:
+ *   avg_out[b][nx], empty_out[b][nx]  the BITS of scint_norm_sspec(sspec_b, ..., row_offset = NULL, xlin = NULL) followed by
+ *                                     scint_masked_colavg(..., weights = 1, rowsel = NULL); the normalised spectrum
+ *                                     norm[nr][nx] in between is never written;
+ *   noise_out[b]                      the BITS of scint_block_std(sspec_b, ld, nc, R / 2, R, noise_lo, noise_hi): fit_arc's
+ *                                     noise before its division by sqrt(2 ind) (its columns are not norm_sspec's cut for an odd
+ *                                     cutmid, hence the two pairs).
+ * A workgroup owns one problem and 256 columns of x and walks the delay rows, summing in the order of scint_masked_colavg
+ * (partials over 32 rows, then the partials in ascending order); a row's selected columns are staged in LDS when there are at most
+ * 2048 of them and read from global memory otherwise.  Six launches for any B, no atomics, asynchronous on `stream`.
+ * workspace: scint_arc_profile_batch_workspace_bytes(B, R, nc, nr) (a table of nr rows, the noise partials). */
+int32_t scint_arc_profile_batch_workspace_bytes(int64_t B, int64_t R, int64_t nc, int64_t nr, size_t* SCINT_HOST bytes);
+int32_t scint_arc_profile_batch(const double* sspec, int64_t B, int64_t R, int64_t ld, int64_t nc, const double* fdop,
+                                const double* yaxis, int64_t row0, int64_t nr, double eta, double maxnormfac,
+                                int64_t cut_lo, int64_t cut_hi, int64_t noise_lo, int64_t noise_hi, const double* x,
+                                int64_t nx, double* avg_out, uint8_t* empty_out, double* noise_out, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
+/* scint_arc_peak_fit: what Dynspec.fit_arc does with a profile after norm_sspec (dynspec.py:1190-1313), one wavefront per profile,
+ * one launch.  avg[P][nx] (the profile kernel's avg_out; nx even, x[nx] ascending with x[nx/2 - 1] < 0 <= x[nx/2], shared),
+ * noise[P] (its noise_out; the fit uses noise[p] / noise_div).  PP = P profiles, or 2 P with asymm: 2 p = the side x >= 0
+ * ("left"), 2 p + 1 = the side x < 0 flipped ("right").  Per profile:
+ *   fold (avg[x >= 0] + flip(avg[x < 0])) / 2 (or one side); drop non-finite entries (a column that empty_out marks carries 0.0
+ *   and is kept); flip; eta = etamin / x^2, keep eta < etamax -> profile_out[PP][nx/2], the kept points, NaN after them;
+ *   smooth: Savitzky-Golay of order 1, interior points with coef[nsmooth] (DEVICE; scipy.signal.savgol_coeffs(nsmooth, 1)), within
+ *   nsmooth/2 of an end the least-squares line over the first / last nsmooth points (scipy's mode='interp'); nsmooth odd, >= 3;
+ *   pk = the first index whose smoothed value equals the largest one with constraint[0] < eta < constraint[1] (HOST [2]);
+ *   i1, i2 = the reference's walks down to low_power_diff / high_power_diff below the peak, bounded by the profile;
+ *   the least-squares parabola through the UNSMOOTHED points [pk - i1, pk + i2) in x 1000 / ptp(x) (log_parabola: in log x,
+ *   scaled twice as fit_log_parabola does), solved through an orthogonal basis on the centred abscissa; peak and peak error from
+ *   the coefficient covariance as scint_models.fit_parabola / fit_log_parabola; noise_error: etaerr from the noise walk.
+ * val_out[4][PP]: eta, etaerr, etaerr2 (both errors divided by sqrt 2, as the attributes are), the noise used.
+ * dec_out[5][PP]: pk, i1, i2 (-1 where not reached), the number of points kept, status:
+ *   0 ok; 1 fewer than max(nsmooth, 4) points kept; 2 no point inside constraint; 3 the window [pk - i1, pk + i2) leaves the
+ *   profile (the reference wraps to negative indices there) or has fewer than 4 points; 4 forward parabola (the reference raises
+ *   ValueError); 5 non-finite result.  Every status but 0 leaves NaN in eta, etaerr and etaerr2.
+ * workspace: scint_arc_peak_fit_workspace_bytes(P, nx, asymm) (the kept curvatures, PP * nx/2 doubles).  No atomics. */
+int32_t scint_arc_peak_fit_workspace_bytes(int64_t P, int64_t nx, int32_t asymm, size_t* SCINT_HOST bytes);
+int32_t scint_arc_peak_fit(const double* avg, int64_t P, int64_t nx, const double* noise, double noise_div,
+                           const double* x, double etamin, double etamax, const double* SCINT_HOST constraint /*[2]*/,
+                           int32_t nsmooth, const double* coef, double low_power_diff, double high_power_diff,
+                           int32_t noise_error, int32_t log_parabola, int32_t asymm, double* profile_out, double* val_out,
+                           int32_t* dec_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- plain 2-D complex FFT (forward, numpy sign convention) -------------- */
 /* Exposed for tests: out may alias in. */

@@ -6,6 +6,8 @@
 * ``Dynspec.norm_sspec``                 dynspec.py:1920-2183  -> ``scint_norm_sspec`` +
                                                                    ``scint_masked_colavg`` (+ ``scint_row_nanmean``)
 * ``Dynspec.fit_arc``                    dynspec.py:970-1313   -> ``scint_block_std`` + norm_sspec
+* ``fit_arc_stack_device`` / ``Dynspec.fit_arc_cut``: fit_arc over a stack -> ``scint_arc_profile_batch`` + ``scint_arc_peak_fit``
+  (there the 1-D profile logic runs on the device too, one wavefront per profile)
 
 The O(rows x columns) work (cubic-spline resample of every time column, the per-delay-row
 ``np.interp`` resample, masked means) runs in HIP kernels; the 1-D profile logic of ``fit_arc``
@@ -13,6 +15,7 @@ The O(rows x columns) work (cubic-spline resample of every time column, the per-
 reference.  Plotting, ``norm_sspec(velocity=True)`` / ``fit_arc(velocity=True)``, ``interp_nan`` (scipy griddata) and
 ``fit_spectrum`` (lmfit) are outside the accelerated path and raise ``NotImplementedError``.
 """
+import collections
 import ctypes
 import warnings
 
@@ -601,6 +604,74 @@ def fit_log_parabola(x, y):
 
 
 # ----------------------------------------------------------------------------
+# the peak of one power-against-curvature profile (dynspec.py:1190-1265)
+# ----------------------------------------------------------------------------
+ArcPeak = collections.namedtuple("ArcPeak", "eta etaerr etaerr2 pk i1 i2 spec eta_array smooth")
+
+
+class ArcWindowError(IndexError):
+    """``_arc_peak(strict=True)``: the fit window [pk - i1, pk + i2) leaves the profile or holds fewer than 4 points."""
+
+
+def _arc_peak(spec, etafrac, etamin, etamax, constraint=(0, np.inf), nsmooth=5, low_power_diff=-1, high_power_diff=-0.5,
+              noise=0.0, noise_error=True, log_parabola=False, strict=False):
+    """What ``fit_arc`` does with one folded profile `spec` over the inverse normalised Doppler axis `etafrac` (both in the order
+    of ``normsspec_fdop >= 0``): drop non-finite entries, flip, ``etaArray = etamin etafrac**2 < etamax``, smooth, find the peak
+    inside `constraint`, walk down to `low_power_diff` / `high_power_diff`, fit the parabola to the unsmoothed points and take the
+    errors.  Returns ``ArcPeak``: eta, etaerr (the noise walk's when `noise_error`, else the fit's), etaerr2 (the fit's) -- not
+    yet divided by sqrt 2 --, pk, i1, i2 (the fit window is [pk - i1, pk + i2)), the kept `spec` and `eta_array`, `smooth`.
+    The lines and the exceptions are the reference's.  ``strict``: where the reference's window would start at a negative index
+    (it wraps) or hold fewer than 4 points, raise ``ArcWindowError`` -- what the batched fit reports as status 3.  That exception and
+    the forward-parabola ``ValueError`` carry ``pk``, ``i1`` and ``i2``."""
+    filt_ind = is_valid(spec)
+    spec = np.flip(spec[filt_ind], axis=0)
+    etafrac_array_avg = np.flip(etafrac[filt_ind], axis=0)
+    etaArray = etamin * etafrac_array_avg**2
+    keep = np.argwhere(etaArray < etamax)
+    etaArray = etaArray[keep].squeeze()
+    spec = spec[keep].squeeze()
+    smooth = savgol_filter(spec, nsmooth, 1)
+    indrange = np.argwhere((etaArray > constraint[0]) * (etaArray < constraint[1]))
+    pk = np.argmin(np.abs(smooth - np.max(smooth[indrange])))
+    max_power = smooth[pk]
+    power, i1 = max_power, 1                 # dynspec.py:1222-1233
+    while power > max_power + low_power_diff and pk + i1 < len(smooth) - 1:
+        i1 += 1
+        power = smooth[pk - i1]
+    power, i2 = max_power, 1
+    while power > max_power + high_power_diff and pk + i2 < len(smooth) - 1:
+        i2 += 1
+        power = smooth[pk + i2]
+    fit_pk, fit_i1, fit_i2 = int(pk), int(i1), int(i2)
+    if strict and (pk - i1 < 0 or i1 + i2 < 4):
+        err = ArcWindowError(f"the fit window [{pk - i1}, {pk + i2}) leaves the profile or holds fewer than 4 points")
+        err.pk, err.i1, err.i2 = fit_pk, fit_i1, fit_i2
+        raise err
+    xdata = etaArray[int(pk - i1):int(pk + i2)]
+    ydata = spec[int(pk - i1):int(pk + i2)]
+    if log_parabola:
+        yfit, eta, etaerr = fit_log_parabola(xdata, ydata)
+    else:
+        yfit, eta, etaerr = fit_parabola(xdata, ydata)
+    if np.mean(np.gradient(np.diff(yfit))) > 0:
+        err = ValueError('Fit returned a forward parabola.')
+        err.pk, err.i1, err.i2 = fit_pk, fit_i1, fit_i2       # (where it happened, for a caller that maps it to a status)
+        raise err
+    etaerr2 = etaerr                         # error from the parabola fit
+    if noise_error:                          # dynspec.py:1250-1265
+        power, i1 = max_power, 1
+        while power > (max_power - noise) and (pk - i1 > 1):
+            power = smooth[pk - i1]
+            i1 += 1
+        power, i2 = max_power, 1
+        while power > (max_power - noise) and (pk + i2 < len(smooth) - 1):
+            i2 += 1
+            power = smooth[pk + i2]
+        etaerr = np.abs(etaArray[int(pk - i1)] - etaArray[int(pk + i2)]) / 2
+    return ArcPeak(eta, etaerr, etaerr2, fit_pk, fit_i1, fit_i2, spec, etaArray, smooth)
+
+
+# ----------------------------------------------------------------------------
 # fit_arc
 # ----------------------------------------------------------------------------
 def fit_arc(self, asymm=False, plot=False, delmax=None, numsteps=1e4, startbin=3, cutmid=3, lamsteps=False,
@@ -678,45 +749,10 @@ def fit_arc(self, asymm=False, plot=False, delmax=None, numsteps=1e4, startbin=3
             etafrac_array_avg_orig = 1 / etafrac_array[ind1].squeeze()
             for dummy, spec in enumerate(profiles):
                 # np.array() drops the mask and keeps what numpy.ma left under it, as the reference does
-                spec = np.array(spec).squeeze()
-                filt_ind = is_valid(spec)
-                spec = np.flip(spec[filt_ind], axis=0)
-                etafrac_array_avg = np.flip(etafrac_array_avg_orig[filt_ind], axis=0)
-                etaArray = etamin * etafrac_array_avg**2
-                keep = np.argwhere(etaArray < etamax)
-                etaArray = etaArray[keep].squeeze()
-                spec = spec[keep].squeeze()
-                smooth = savgol_filter(spec, nsmooth, 1)
-                indrange = np.argwhere((etaArray > constraint[0]) * (etaArray < constraint[1]))
-                pk = np.argmin(np.abs(smooth - np.max(smooth[indrange])))
-                max_power = smooth[pk]
-                power, i1 = max_power, 1                 # dynspec.py:1222-1233
-                while power > max_power + low_power_diff and pk + i1 < len(smooth) - 1:
-                    i1 += 1
-                    power = smooth[pk - i1]
-                power, i2 = max_power, 1
-                while power > max_power + high_power_diff and pk + i2 < len(smooth) - 1:
-                    i2 += 1
-                    power = smooth[pk + i2]
-                xdata = etaArray[int(pk - i1):int(pk + i2)]
-                ydata = spec[int(pk - i1):int(pk + i2)]
-                if log_parabola:
-                    yfit, eta, etaerr = fit_log_parabola(xdata, ydata)
-                else:
-                    yfit, eta, etaerr = fit_parabola(xdata, ydata)
-                if np.mean(np.gradient(np.diff(yfit))) > 0:
-                    raise ValueError('Fit returned a forward parabola.')
-                etaerr2 = etaerr                         # error from the parabola fit
-                if noise_error:                          # dynspec.py:1250-1265
-                    power, i1 = max_power, 1
-                    while power > (max_power - noise) and (pk - i1 > 1):
-                        power = smooth[pk - i1]
-                        i1 += 1
-                    power, i2 = max_power, 1
-                    while power > (max_power - noise) and (pk + i2 < len(smooth) - 1):
-                        i2 += 1
-                        power = smooth[pk + i2]
-                    etaerr = np.abs(etaArray[int(pk - i1)] - etaArray[int(pk + i2)]) / 2
+                peak = _arc_peak(np.array(spec).squeeze(), etafrac_array_avg_orig, etamin, etamax, constraint=constraint,
+                                 nsmooth=nsmooth, low_power_diff=low_power_diff, high_power_diff=high_power_diff, noise=noise,
+                                 noise_error=noise_error, log_parabola=log_parabola)
+                eta, etaerr, etaerr2, spec, etaArray = peak.eta, peak.etaerr, peak.etaerr2, peak.spec, peak.eta_array
                 self.eta_array = etaArray
                 sigma = self.noise * efac
                 prob = 1 / (sigma * np.sqrt(2 * np.pi)) * np.exp(-0.5 * ((spec - np.max(spec)) / sigma)**2)
@@ -736,6 +772,186 @@ def fit_arc(self, asymm=False, plot=False, delmax=None, numsteps=1e4, startbin=3
             self.norm_delmax = delmax
     finally:
         self._arc_dev_cache = None
+
+
+# ----------------------------------------------------------------------------
+# fit_arc over a stack of spectra (csrc/arcbatch.hpp)
+# ----------------------------------------------------------------------------
+ARC_OK, ARC_SHORT, ARC_NO_RANGE, ARC_WINDOW, ARC_FORWARD, ARC_NONFINITE = range(6)
+ARC_STATUS_TEXT = {ARC_OK: "ok", ARC_SHORT: "fewer than max(nsmooth, 4) points kept", ARC_NO_RANGE: "no point inside the constraint",
+                   ARC_WINDOW: "the fit window leaves the profile or holds fewer than 4 points",
+                   ARC_FORWARD: "the fit returned a forward parabola", ARC_NONFINITE: "non-finite result"}
+
+
+def arc_profile_stack_device(sspec_stack_t, fdop_t, yaxis_t, row0, nr, eta, maxnormfac, cut_lo, cut_hi, noise_lo, noise_hi, x_t):
+    """``scint_arc_profile_batch`` on device tensors: (avg [B, nx], empty [B, nx] uint8, noise [B]), problem b with the bits of
+    ``scint_norm_sspec`` + ``scint_masked_colavg`` (unit weights) and of ``scint_block_std`` over the outer half in delay."""
+    B, R, nc = (int(v) for v in sspec_stack_t.shape)
+    nx = int(x_t.shape[0])
+    avg_t = empty((B, nx), torch.float64)
+    none_t = empty((B, nx), torch.uint8)
+    noise_t = empty((B,), torch.float64)
+    ws = workspace_for("scint_arc_profile_batch", B, R, nc, nr)
+    _lib.call("scint_arc_profile_batch", sspec_stack_t, B, R, nc, nc, fdop_t, yaxis_t, row0, nr, eta, maxnormfac, cut_lo, cut_hi,
+              noise_lo, noise_hi, x_t, nx, avg_t, none_t, noise_t, ws, ws.numel(), stream_ptr())
+    return avg_t, none_t, noise_t
+
+
+def arc_peak_fit_device(avg_t, noise_t, noise_div, x_t, etamin, etamax, constraint=(0, np.inf), nsmooth=5, low_power_diff=-1,
+                        high_power_diff=-0.5, noise_error=True, log_parabola=False, asymm=False):
+    """``scint_arc_peak_fit`` on device tensors: (profile [PP, nx/2], val [4, PP], dec [5, PP]) on the device, PP = P or 2 P."""
+    from scipy.signal import savgol_coeffs
+    P, nx = (int(v) for v in avg_t.shape)
+    npp = P * (2 if asymm else 1)
+    coef_t = to_device(np.ascontiguousarray(savgol_coeffs(nsmooth, 1), dtype=float), torch.float64)
+    prof_t = empty((npp, nx // 2), torch.float64)
+    val_t = empty((4, npp), torch.float64)
+    dec_t = empty((5, npp), torch.int32)
+    ws = workspace_for("scint_arc_peak_fit", P, nx, int(bool(asymm)))
+    _lib.call("scint_arc_peak_fit", avg_t, P, nx, noise_t, noise_div, x_t, etamin, etamax,
+              np.array([constraint[0], constraint[1]], dtype=float), nsmooth, coef_t, low_power_diff, high_power_diff,
+              int(bool(noise_error)), int(bool(log_parabola)), int(bool(asymm)), prof_t, val_t, dec_t, ws, ws.numel(), stream_ptr())
+    return prof_t, val_t, dec_t
+
+
+def fit_arc_stack_device(sspec_stack_t, fdop, yaxis, etamin=None, etamax=None, delmax=None, numsteps=1e4, startbin=3, cutmid=3,
+                         constraint=(0, np.inf), nsmooth=5, efac=1, noise_error=True, log_parabola=False, logsteps=False,
+                         asymm=False, low_power_diff=-1, high_power_diff=-0.5, out_device=False, weighted=False,
+                         subtract_artefacts=False, fit_spectrum=False):
+    """``fit_arc`` for every spectrum of the device stack ``sspec_stack_t [B, R, nc]`` (dB) with the shared axes `fdop` [nc]
+    (ascending) and `yaxis` [R]: two kernels (``scint_arc_profile_batch``, ``scint_arc_peak_fit``), seven launches and two small
+    read-backs however large B is.  Curvatures are in units of ``yaxis / fdop**2``: there is no reference-frequency conversion.
+
+    The defaults are ``fit_arc``'s formulas, with ``ymax = yaxis[ind]``, ``ind = argmin |yaxis - delmax|``:
+    ``etamax = ymax / ((fdop[1] - fdop[0]) cutmid)**2`` (``cutmid = 0`` without ``etamax`` is a ValueError) and
+    ``etamin = (yaxis[1] - yaxis[0]) startbin / max(fdop)**2``; the normalised Doppler grid is the one ``fit_arc`` ->
+    ``norm_sspec(eta=etamin, maxnormfac=1, numsteps=len(sqrt_eta))`` builds, ``logsteps`` included.
+
+    Returns a dict: ``eta, etaerr, etaerr2`` ([B], or [B, 2] with ``asymm``: left, right; both errors divided by sqrt 2 as the
+    attributes of ``fit_arc`` are, NaN where ``status`` is not 0), ``status`` (``ARC_*``), ``noise`` [B], ``pk, i1, i2, kept``
+    (the peak index, the fit window [pk - i1, pk + i2) and the number of points of each profile), ``eta_array`` (the curvature
+    grid of a profile without non-finite entries; a profile that lost some has ``kept`` points on its own shorter grid) and
+    ``profile`` ([B(, 2), nx/2], the folded power-against-curvature curves, NaN after the ``kept`` points; a device tensor with
+    ``out_device``).  ``efac`` is accepted for ``fit_arc``'s signature; the probability curves it scales are not formed.
+
+    Outside the batched path, each a ``NotImplementedError``: ``weighted=True``, ``subtract_artefacts``, ``fit_spectrum`` and
+    array-valued ``etamin`` / ``etamax`` (several arcs)."""
+    if weighted:
+        raise NotImplementedError("fit_arc_stack_device: weighted=True (the power-spectrum weights of norm_sspec) is outside the batched path")
+    if subtract_artefacts:
+        raise NotImplementedError("fit_arc_stack_device: subtract_artefacts is outside the batched path")
+    if fit_spectrum:
+        raise NotImplementedError("fit_spectrum needs lmfit and is outside the accelerated path")
+    if np.ndim(etamin) > 0 or np.ndim(etamax) > 0:
+        raise NotImplementedError("fit_arc_stack_device: array-valued etamin / etamax (several arcs) are outside the batched path")
+    if not isinstance(sspec_stack_t, torch.Tensor) or sspec_stack_t.dim() != 3:
+        raise ValueError("fit_arc_stack_device: the stack must be a device tensor [B, R, nc]")
+    if sspec_stack_t.dtype != torch.float64 or not sspec_stack_t.is_contiguous():
+        raise ValueError("fit_arc_stack_device: the stack must be a contiguous float64 tensor")
+    B, R, nc = (int(v) for v in sspec_stack_t.shape)
+    if B < 1 or B > 65535:
+        raise ValueError(f"fit_arc_stack_device: 1 to 65535 spectra in a stack ({B} given)")
+    fdop = np.asarray(fdop, dtype=float)
+    yaxis = np.asarray(yaxis, dtype=float)
+    if fdop.shape != (nc,) or yaxis.shape != (R,) or R < 2 or nc < 2:
+        raise ValueError(f"fit_arc_stack_device: spectra of {R} x {nc} with {len(yaxis)} delays and {len(fdop)} Doppler bins")
+    if np.any(np.diff(fdop) <= 0):
+        raise ValueError("fit_arc_stack_device: the fdop axis must be ascending")
+    nsmooth = int(nsmooth)
+    if nsmooth < 3 or nsmooth % 2 == 0:
+        raise ValueError("fit_arc_stack_device: nsmooth must be odd and at least 3")
+    if cutmid == 0 and etamax is None:
+        raise ValueError("fit_arc_stack_device: cutmid = 0 needs an explicit etamax (the default divides by cutmid)")
+    require_gpu()
+    delmax = np.max(yaxis) if delmax is None else delmax
+    ind = int(np.argmin(abs(yaxis - delmax)))
+    ymax = yaxis[ind]
+    if ind < 1:
+        raise ValueError("fit_arc_stack_device: delmax leaves no delay row")
+    noise_hi = int(nc / 2 + np.ceil(cutmid / 2))                 # fit_arc's noise columns (dynspec.py:1097-1101)
+    noise_lo = int(nc / 2 - np.floor(cutmid / 2))
+    noise_div = float(np.sqrt(len(yaxis[0:ind]) * 2))
+    if etamax is None:
+        etamax = ymax / ((fdop[1] - fdop[0]) * cutmid)**2
+    if etamin is None:
+        etamin = (yaxis[1] - yaxis[0]) * startbin / (max(fdop))**2
+    etamin, etamax = float(etamin), float(etamax)
+    sqrt_eta_all = np.linspace(np.sqrt(etamin), np.sqrt(etamax), int(numsteps))
+    sqrt_eta = sqrt_eta_all[(sqrt_eta_all <= np.sqrt(etamax)) * (sqrt_eta_all >= np.sqrt(etamin))]
+    # the grid of norm_sspec(eta=etamin, maxnormfac=1, numsteps=len(sqrt_eta)) (dynspec.py:2065-2091)
+    row0 = int(startbin)
+    nr = len(range(R)[startbin:ind])
+    if nr < 1:
+        raise IndexError("index -1 is out of bounds for axis 0 with size 0")
+    tdel = yaxis[startbin:ind]
+    cut_lo = int(nc / 2 - np.floor(cutmid / 2))
+    cut_hi = int(nc / 2 + np.floor(cutmid / 2))
+    nfdop = len(sqrt_eta)
+    if nfdop % 2 != 0:
+        nfdop += 1
+    if logsteps:
+        fdoplin = np.abs(np.linspace(-1, 1, int(nfdop)))
+        fdop_pos = 10**np.linspace(np.log10(np.min(fdoplin)), np.log10(np.max(fdoplin)), int(nfdop / 2))
+        fdopnew = np.concatenate((-np.flip(fdop_pos, axis=0), fdop_pos))
+    else:
+        fdopnew = np.linspace(-1, 1, int(nfdop))
+    if not np.any(abs(fdop) <= np.sqrt(np.min(tdel) / etamin)):
+        raise ValueError("array of sample points is empty")
+    x = np.ascontiguousarray(fdopnew, dtype=float)
+    half = len(x) // 2
+    if len(x) < 2 or not (x[half - 1] < 0 <= x[half]):
+        raise ValueError("fit_arc_stack_device: the normalised Doppler grid is not symmetric")
+    fdop_t, yaxis_t, x_t = (to_device(v, torch.float64) for v in (fdop, yaxis, x))
+    avg_t, none_t, noise_t = arc_profile_stack_device(sspec_stack_t, fdop_t, yaxis_t, row0, nr, etamin, 1.0, cut_lo, cut_hi,
+                                                      noise_lo, noise_hi, x_t)
+    prof_t, val_t, dec_t = arc_peak_fit_device(avg_t, noise_t, noise_div, x_t, etamin, etamax, constraint=constraint,
+                                               nsmooth=nsmooth, low_power_diff=low_power_diff, high_power_diff=high_power_diff,
+                                               noise_error=noise_error, log_parabola=log_parabola, asymm=asymm)
+    val = val_t.cpu().numpy()                                    # the two read-backs
+    dec = dec_t.cpu().numpy()
+    shape = (B, 2) if asymm else (B,)
+    eta_array = etamin * np.flip(1 / x[half:], axis=0)**2
+    out = {"eta": val[0].reshape(shape), "etaerr": val[1].reshape(shape), "etaerr2": val[2].reshape(shape),
+           "noise": val[3].reshape(shape)[:, 0].copy() if asymm else val[3].copy(),
+           "pk": dec[0].reshape(shape), "i1": dec[1].reshape(shape), "i2": dec[2].reshape(shape), "kept": dec[3].reshape(shape),
+           "status": dec[4].reshape(shape), "eta_array": eta_array[eta_array < etamax]}
+    prof_t = prof_t.view(shape + (half,))
+    out["profile"] = prof_t if out_device else prof_t.cpu().numpy()
+    return out
+
+
+def fit_arc_cut(self, tcuts=0, fcuts=0, **kwargs):
+    """``fit_arc`` of every segment of ``cut_dyn(tcuts, fcuts)`` in one batched call (``fit_arc_stack_device`` and its keywords) on
+    ``cutsspec`` as it sits in HBM; ``cut_dyn`` runs first if ``cutsspec`` is absent or belongs to another cut.  The axes are a
+    segment's ``fdop`` and ``tdel`` as ``calc_sspec(input_dyn=segment)`` returns them, so curvatures are in us / mHz**2 without a
+    reference-frequency conversion.  Sets ``cut_eta, cut_etaerr, cut_etaerr2, cut_arc_status`` ([fcuts + 1, tcuts + 1], with
+    ``asymm`` [.., 2]: left, right), ``cut_arc_noise`` [fcuts + 1, tcuts + 1], ``cut_eta_array`` and ``cut_arc_profile`` (the folded profiles [fcuts + 1, tcuts + 1(, 2), nx/2]:
+    a device tensor, 164 MB for 4096 segments, or a NumPy array with ``out_device=False``); warns once with the count when a
+    segment's status is not 0 (its values are NaN)."""
+    cls = type(self)
+    fnum = int(np.floor(len(self.freqs) / (fcuts + 1)))
+    tnum = int(np.floor(len(self.times) / (tcuts + 1)))
+    if fcuts < 0 or tcuts < 0 or fnum < 2 or tnum < 5:
+        raise ValueError(f"fit_arc_cut: segments of {fnum} channels x {tnum} sub-integrations are too small (at least 2 x 5)")
+    nrfft = int(2**(np.ceil(np.log2(fnum)) + 1))
+    ncfft = int(2**(np.ceil(np.log2(tnum)) + 1))
+    shape = (fcuts + 1, tcuts + 1)
+    if not cls.cutsspec.present(self) or tuple(cls.cutsspec.shape(self)) != shape + (nrfft // 2, ncfft):
+        self.cut_dyn(tcuts=tcuts, fcuts=fcuts)
+    fdop = np.arange(int(-ncfft / 2), int(ncfft / 2)) * (1e3 / (ncfft * self.dt))      # calc_sspec's axes for a segment
+    tdel = np.arange(0, int(nrfft / 2)) / (nrfft * self.df)
+    stack_t = cls.cutsspec.tensor(self).view(shape[0] * shape[1], nrfft // 2, ncfft)
+    kwargs.setdefault("out_device", True)                        # unless asked for, the profiles stay in HBM
+    fit = fit_arc_stack_device(stack_t, fdop, tdel, **kwargs)
+    full = shape + ((2,) if kwargs.get("asymm") else ())
+    self.cut_eta, self.cut_etaerr, self.cut_etaerr2 = (fit[k].reshape(full) for k in ("eta", "etaerr", "etaerr2"))
+    self.cut_arc_status = fit["status"].reshape(full)
+    self.cut_arc_noise = fit["noise"].reshape(shape)
+    self.cut_eta_array = fit["eta_array"]
+    self.cut_arc_profile = fit["profile"].reshape(full + (-1,))
+    bad = int(np.count_nonzero(self.cut_arc_status))
+    if bad:
+        warnings.warn(f"fit_arc_cut: {bad} of {self.cut_arc_status.size} arc fits did not succeed (cut_arc_status; their values are NaN)")
 
 
 # ----------------------------------------------------------------------------

@@ -110,52 +110,63 @@ struct NormRow {
         const double v = gload(row + c);
         return has_offset ? v - offset : v;
     }
-    // np.interp(x, xp, fp) for one x (numpy/_core/src/multiarray/compiled_base.c, arr_interp)
-    __device__ inline double interp(double x, double x_lo, double x_hi, double inv_step) const {
-        const int64_t n = c1 - c0 + 1;
-        if (n == 1) return fp(c0);
-        if (x != x) return x;
-        if (x > x_hi) return fp(c1);
-        if (x < x_lo) return fp(c0);
-        // j = largest column with xp(j) <= x: uniform-axis guess, short walk, bisection fallback.
-        // xp(j) and xp(j+1) are carried along so that the usual case costs two divisions.
-        const double g = floor((x - x_lo) * inv_step);
-        int64_t j = c0 + (int64_t)fmin(fmax(g, 0.0), (double)(n - 1));
-        double xj = xp(j), xj1 = 0.0;
-        bool have1 = false;
-        int walk = 0;
-        while (xj > x && j > c0 && walk < 6) { xj1 = xj; have1 = true; --j; xj = xp(j); ++walk; }
-        if (!(xj > x)) {
-            while (j < c1 && walk < 6) {
-                if (!have1) { xj1 = xp(j + 1); have1 = true; }
-                if (xj1 > x) break;
-                ++j; xj = xj1; have1 = false; ++walk;
-            }
-        }
-        if (xj > x || (j < c1 && (have1 ? xj1 : xp(j + 1)) <= x)) {
-            int64_t lo = c0, hi = c1 + 1;  // first column with xp > x is in (lo, hi]
-            while (lo < hi) {
-                const int64_t mid = lo + ((hi - lo) >> 1);
-                if (x >= xp(mid)) lo = mid + 1; else hi = mid;
-            }
-            j = lo - 1;
-            xj = xp(j);
-            have1 = false;
-        }
-        if (j == c1) return fp(j);
-        const double fj = fp(j);
-        if (xj == x) return fj;
-        if (!have1) xj1 = xp(j + 1);
-        const double fj1 = fp(j + 1);
-        const double slope = (fj1 - fj) / (xj1 - xj);
-        double r = slope * (x - xj) + fj;
-        if (r != r) {
-            r = slope * (x - xj1) + fj1;
-            if (r != r && fj == fj1) r = fj;
-        }
-        return r;
-    }
+    __device__ inline double interp(double x, double x_lo, double x_hi, double inv_step) const;
 };
+
+// np.interp(x, xp, fp) for one x (numpy/_core/src/multiarray/compiled_base.c, arr_interp) over the selected columns [c0, c1] of a
+// row: `Row` gives c0, c1, the abscissa xp(c) and the value fp(c) (NormRow from global memory; the batched profile's tile from LDS)
+template <class Row>
+__device__ inline double interp_row(const Row& row, double x, double x_lo, double x_hi, double inv_step) {
+    const int64_t c0 = row.c0, c1 = row.c1;
+    auto xp = [&](int64_t c) { return row.xp(c); };
+    auto fp = [&](int64_t c) { return row.fp(c); };
+    const int64_t n = c1 - c0 + 1;
+    if (n == 1) return fp(c0);
+    if (x != x) return x;
+    if (x > x_hi) return fp(c1);
+    if (x < x_lo) return fp(c0);
+    // j = largest column with xp(j) <= x: uniform-axis guess, short walk, bisection fallback.
+    // xp(j) and xp(j+1) are carried along so that the usual case costs two divisions.
+    const double g = floor((x - x_lo) * inv_step);
+    int64_t j = c0 + (int64_t)fmin(fmax(g, 0.0), (double)(n - 1));
+    double xj = xp(j), xj1 = 0.0;
+    bool have1 = false;
+    int walk = 0;
+    while (xj > x && j > c0 && walk < 6) { xj1 = xj; have1 = true; --j; xj = xp(j); ++walk; }
+    if (!(xj > x)) {
+        while (j < c1 && walk < 6) {
+            if (!have1) { xj1 = xp(j + 1); have1 = true; }
+            if (xj1 > x) break;
+            ++j; xj = xj1; have1 = false; ++walk;
+        }
+    }
+    if (xj > x || (j < c1 && (have1 ? xj1 : xp(j + 1)) <= x)) {
+        int64_t lo = c0, hi = c1 + 1;  // first column with xp > x is in (lo, hi]
+        while (lo < hi) {
+            const int64_t mid = lo + ((hi - lo) >> 1);
+            if (x >= xp(mid)) lo = mid + 1; else hi = mid;
+        }
+        j = lo - 1;
+        xj = xp(j);
+        have1 = false;
+    }
+    if (j == c1) return fp(j);
+    const double fj = fp(j);
+    if (xj == x) return fj;
+    if (!have1) xj1 = xp(j + 1);
+    const double fj1 = fp(j + 1);
+    const double slope = (fj1 - fj) / (xj1 - xj);
+    double r = slope * (x - xj) + fj;
+    if (r != r) {
+        r = slope * (x - xj1) + fj1;
+        if (r != r && fj == fj1) r = fj;
+    }
+    return r;
+}
+
+__device__ inline double NormRow::interp(double x, double x_lo, double x_hi, double inv_step) const {
+    return interp_row(*this, x, x_lo, x_hi, inv_step);
+}
 
 struct NormParams {
     const double* sspec; int64_t ld, nc;
@@ -275,14 +286,17 @@ row_nanmean_kernel(const double* sspec, int64_t ld, int64_t nc, int64_t row0, co
 
 constexpr int kStdBlocks = 1024;
 
-// pass 0: sum(x); pass 1: sum((x - mean)^2), mean = *mean_p
+// pass 0: sum(x); pass 1: sum((x - mean)^2), mean = mean_p[problem].  blockIdx.y = the problem of a stack (array `stride`, partials
+// `pstride` apart; one problem: grid.y = 1)
 __global__ void __launch_bounds__(256)
-block_moment_kernel(const double* a, int64_t ld, int64_t r0, int64_t rows, int64_t c_lo, int64_t c_hi,
-                    int64_t nc, const double* mean_p, double* partial) {
+block_moment_kernel(const double* a, int64_t stride, int64_t ld, int64_t r0, int64_t rows, int64_t c_lo, int64_t c_hi,
+                    int64_t nc, const double* mean_p, double* partial, int64_t pstride) {
     __shared__ double red[4];
+    const int64_t b = blockIdx.y;
+    a += b * stride;
     const int64_t width = c_lo + (nc - c_hi);
     const int64_t total = rows * width;
-    const double mean = mean_p ? mean_p[0] : 0.0;
+    const double mean = mean_p ? mean_p[b] : 0.0;
     double acc = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t r = i / width, q = i - r * width;
@@ -291,16 +305,18 @@ block_moment_kernel(const double* a, int64_t ld, int64_t r0, int64_t rows, int64
         acc += mean_p ? (v - mean) * (v - mean) : v;
     }
     acc = block_sum(acc, red);
-    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+    if (threadIdx.x == 0) partial[b * pstride + blockIdx.x] = acc;
 }
 
+// blockIdx.x = the problem
 __global__ void __launch_bounds__(256)
-block_moment_final_kernel(const double* partial, int np, double inv_n, int take_sqrt, double* out) {
+block_moment_final_kernel(const double* partial, int64_t pstride, int np, double inv_n, int take_sqrt, double* out) {
     __shared__ double red[4];
+    const int64_t b = blockIdx.x;
     double acc = 0.0;
-    for (int i = threadIdx.x; i < np; i += 256) acc += partial[i];
+    for (int i = threadIdx.x; i < np; i += 256) acc += partial[b * pstride + i];
     acc = block_sum(acc, red);
-    if (threadIdx.x == 0) out[0] = take_sqrt ? sqrt(acc * inv_n) : acc * inv_n;
+    if (threadIdx.x == 0) out[b] = take_sqrt ? sqrt(acc * inv_n) : acc * inv_n;
 }
 
 }  // namespace scint
@@ -308,6 +324,7 @@ block_moment_final_kernel(const double* partial, int np, double inv_n, int take_
 #include "scatim.hpp"
 #include "clean.hpp"
 #include "inpaint.hpp"
+#include "arcbatch.hpp"
 
 using namespace scint;
 
@@ -425,10 +442,10 @@ extern "C" int32_t scint_block_std(const double* a, int64_t ld, int64_t nc, int6
     double* mean = partial + kStdBlocks;
     const int blocks = (int)std::min<int64_t>(kStdBlocks, std::max<int64_t>(1, ceil_div(total, 1024)));
     for (int pass = 0; pass < 2; ++pass) {
-        hipLaunchKernelGGL(block_moment_kernel, dim3(blocks), dim3(256), 0, stream, a, ld, r0, r1 - r0, c_lo, c_hi,
-                           nc, pass ? mean : (const double*)nullptr, partial);
+        hipLaunchKernelGGL(block_moment_kernel, dim3(blocks), dim3(256), 0, stream, a, (int64_t)0, ld, r0, r1 - r0, c_lo, c_hi,
+                           nc, pass ? mean : (const double*)nullptr, partial, (int64_t)0);
         SCINT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(block_moment_final_kernel, dim3(1), dim3(256), 0, stream, partial, blocks,
+        hipLaunchKernelGGL(block_moment_final_kernel, dim3(1), dim3(256), 0, stream, (const double*)partial, (int64_t)0, blocks,
                            1.0 / (double)total, pass, pass ? out : mean);
         SCINT_LAUNCH_CHECK();
     }
@@ -768,6 +785,93 @@ extern "C" int32_t scint_inpaint_biharmonic(double* dyn, int64_t nf, int64_t nt,
     if (residual_out) *residual_out = h.bnorm2 > 0.0 ? sqrt(h.true_rho / h.bnorm2) : 0.0;
     if (!ok) { set_error("scint: inpaint_biharmonic: conjugate gradients did not reach the residual"); return SCINT_E_NOCONV; }
     hipLaunchKernelGGL(inpaint_scatter_kernel, dim3(nb), dim3(256), 0, stream, (const double*)x, (const int32_t*)list, n, dyn);
+    SCINT_LAUNCH_CHECK();
+    return SCINT_OK;
+}
+
+// ------------------------------------------------------------------------------
+// arc fits over a stack of spectra (kernels: arcbatch.hpp)
+// ------------------------------------------------------------------------------
+static int arc_std_blocks(int64_t total) { return (int)std::min<int64_t>(kStdBlocks, std::max<int64_t>(1, ceil_div(total, 1024))); }
+
+extern "C" int32_t scint_arc_profile_batch_workspace_bytes(int64_t B, int64_t R, int64_t nc, int64_t nr, size_t* bytes) {
+    SCINT_REQUIRE(bytes && B >= 1 && B <= 65535 && R >= 2 && nc >= 1 && nr >= 1 && nr <= R,
+                  "arc_profile_batch_workspace_bytes: bad arguments");
+    // the row table; per problem the partials of the widest possible noise selection
+    const size_t pstride = (size_t)arc_std_blocks((R - R / 2) * nc);
+    *bytes = align_up(sizeof(ArcRowInfo) * (size_t)nr, 256) + align_up(sizeof(double) * (size_t)B * pstride, 256);
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_arc_profile_batch(const double* sspec, int64_t B, int64_t R, int64_t ld, int64_t nc, const double* fdop,
+                                           const double* yaxis, int64_t row0, int64_t nr, double eta, double maxnormfac,
+                                           int64_t cut_lo, int64_t cut_hi, int64_t noise_lo, int64_t noise_hi, const double* x,
+                                           int64_t nx, double* avg_out, uint8_t* empty_out, double* noise_out, void* workspace,
+                                           size_t workspace_bytes, void* stream_) {
+    SCINT_REQUIRE(sspec && fdop && yaxis && x && avg_out && empty_out && noise_out && workspace, "arc_profile_batch: null pointer");
+    SCINT_REQUIRE(B >= 1 && B <= 65535, "arc_profile_batch: 1 to 65535 problems");
+    SCINT_REQUIRE(R >= 2 && nc >= 1 && ld >= nc && nx >= 1, "arc_profile_batch: bad sizes");
+    SCINT_REQUIRE(row0 >= 0 && nr >= 1 && row0 + nr <= R, "arc_profile_batch: the delay rows leave the spectrum");
+    SCINT_REQUIRE(noise_lo >= 0 && noise_hi >= noise_lo && noise_hi <= nc && noise_lo + nc - noise_hi >= 1,
+                  "arc_profile_batch: bad noise columns");
+    size_t need = 0;
+    scint_arc_profile_batch_workspace_bytes(B, R, nc, nr, &need);
+    if (workspace_bytes < need) { set_error("scint: arc_profile_batch workspace too small"); return SCINT_E_WORKSPACE; }
+    hipStream_t stream = (hipStream_t)stream_;
+    Carver carve(workspace, workspace_bytes);
+    ArcRowInfo* table = carve.take<ArcRowInfo>((size_t)nr);
+    const int64_t pstride = arc_std_blocks((R - R / 2) * nc);
+    double* partial = carve.take<double>((size_t)B * pstride);
+    hipLaunchKernelGGL(arc_row_table_kernel, dim3((unsigned)ceil_div(nr, 256)), dim3(256), 0, stream, fdop, nc, yaxis, row0, nr, eta,
+                       maxnormfac, table);
+    SCINT_LAUNCH_CHECK();
+    ArcProfileParams p;
+    p.sspec = sspec; p.stride = R * ld; p.ld = ld; p.fdop = fdop; p.row0 = row0; p.nr = nr; p.cut_lo = cut_lo; p.cut_hi = cut_hi;
+    p.rows = table; p.x = x; p.nx = nx; p.avg = avg_out; p.empty = empty_out;
+    hipLaunchKernelGGL(arc_profile_kernel, dim3((unsigned)ceil_div(nx, 256), (unsigned)B), dim3(256), 0, stream, p);
+    SCINT_LAUNCH_CHECK();
+    // the noise of every problem: the two passes of scint_block_std over rows [R/2, R)
+    const int64_t r0 = R / 2, rows = R - r0, total = rows * (noise_lo + nc - noise_hi);
+    const int blocks = arc_std_blocks(total);
+    for (int pass = 0; pass < 2; ++pass) {
+        // (between the passes noise_out[b] holds the mean of problem b)
+        hipLaunchKernelGGL(block_moment_kernel, dim3(blocks, (unsigned)B), dim3(256), 0, stream, sspec, R * ld, ld, r0, rows, noise_lo,
+                           noise_hi, nc, pass ? (const double*)noise_out : (const double*)nullptr, partial, pstride);
+        SCINT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(block_moment_final_kernel, dim3((unsigned)B), dim3(256), 0, stream, (const double*)partial, pstride, blocks,
+                           1.0 / (double)total, pass, noise_out);
+        SCINT_LAUNCH_CHECK();
+    }
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_arc_peak_fit_workspace_bytes(int64_t P, int64_t nx, int32_t asymm, size_t* bytes) {
+    SCINT_REQUIRE(bytes && P >= 1 && P * (asymm ? 2 : 1) <= 0x7fffffff && nx >= 2 && nx % 2 == 0,
+                  "arc_peak_fit_workspace_bytes: bad arguments");
+    *bytes = align_up(sizeof(double) * (size_t)P * (asymm ? 2 : 1) * (size_t)(nx / 2), 256);
+    return SCINT_OK;
+}
+
+extern "C" int32_t scint_arc_peak_fit(const double* avg, int64_t P, int64_t nx, const double* noise, double noise_div,
+                                      const double* x, double etamin, double etamax, const double* constraint, int32_t nsmooth,
+                                      const double* coef, double low_power_diff, double high_power_diff, int32_t noise_error,
+                                      int32_t log_parabola, int32_t asymm, double* profile_out, double* val_out, int32_t* dec_out,
+                                      void* workspace, size_t workspace_bytes, void* stream_) {
+    SCINT_REQUIRE(avg && noise && x && constraint && coef && profile_out && val_out && dec_out && workspace,
+                  "arc_peak_fit: null pointer");
+    SCINT_REQUIRE(P >= 1 && P <= 0x7fffffff && P * (asymm ? 2 : 1) <= 0x7fffffff, "arc_peak_fit: 1 to 2^31 - 1 profiles (two per problem with asymm)");
+    SCINT_REQUIRE(nx >= 2 && nx % 2 == 0, "arc_peak_fit: x must hold as many negative as non-negative entries");
+    SCINT_REQUIRE(nsmooth >= 3 && (nsmooth & 1), "arc_peak_fit: nsmooth must be odd and at least 3");
+    SCINT_REQUIRE(noise_div > 0.0, "arc_peak_fit: bad noise divisor");
+    size_t need = 0;
+    scint_arc_peak_fit_workspace_bytes(P, nx, asymm, &need);
+    if (workspace_bytes < need) { set_error("scint: arc_peak_fit workspace too small"); return SCINT_E_WORKSPACE; }
+    ArcPeakParams p;
+    p.avg = avg; p.nx = nx; p.noise = noise; p.noise_div = noise_div; p.x = x; p.etamin = etamin; p.etamax = etamax;
+    p.con_lo = constraint[0]; p.con_hi = constraint[1]; p.nsmooth = nsmooth; p.coef = coef; p.low = low_power_diff;
+    p.high = high_power_diff; p.noise_error = noise_error; p.log_parabola = log_parabola; p.asymm = asymm ? 1 : 0;
+    p.prof = profile_out; p.etak = (double*)workspace; p.val = val_out; p.dec = dec_out; p.npp = P * (asymm ? 2 : 1);
+    hipLaunchKernelGGL(arc_peak_fit_kernel, dim3((unsigned)p.npp), dim3(64), 0, (hipStream_t)stream_, p);
     SCINT_LAUNCH_CHECK();
     return SCINT_OK;
 }

@@ -340,6 +340,7 @@ class Dynspec:
     cut_dyn = scintpar.cut_dyn
     fit_scint_params = scintpar.fit_scint_params
     fit_scint_params_cut = scintpar.fit_scint_params_cut
+    fit_arc_cut = arcfit.fit_arc_cut
     fit_scint_params_2d = scintpar.fit_scint_params_2d
     fit_scint_params_2d_cut = scintpar.fit_scint_params_2d_cut
 
