@@ -1031,7 +1031,7 @@ static int32_t fft2_general(RowSource src, int64_t nvalid, double fill0, int64_t
 // A stack whose problems are beyond the cache takes the tiled column passes (run_cols_fft), which number their tile slots in 32 bits:
 // the limit an entry point for stacks checks with its shape, so that it is an argument error there and not deep inside the call.
 static bool stack_cols_ok(int64_t B, int64_t R, int64_t C) {
-    return (double)R * (double)C * 16.0 <= 300.0 * 1048576.0 || B * ceil_div(C, 16) * 128 < ((int64_t)1 << 32);
+    return (double)R * (double)C * 16.0 <= kColsCacheBytes || B * ceil_div(C, 16) * 128 < ((int64_t)1 << 32);
 }
 static size_t fft2_general_ws(int64_t R, int64_t C, int64_t nvalid, int64_t B = 1) { return make_plan(R, C, nvalid, B).total; }
 

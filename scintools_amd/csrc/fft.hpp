@@ -539,6 +539,10 @@ int32_t launch_cols_pass(const ColPass& p, int64_t batches, Loader ld, Storer st
 // Index arithmetic is 32-bit (rows, columns, strides and tile counts are far below 2^31; only the
 // final element offset is 64-bit): a 64-bit multiply is four quarter-rate instructions on CDNA, and
 // these kernels issue one address per 16-byte element.
+#ifndef SCINT_COLS_CACHE_BYTES
+#define SCINT_COLS_CACHE_BYTES (300.0 * 1048576.0)   // working arrays above this take the tiled passes (run_cols_fft, where it was measured);
+#endif                                               // a build constant so that a test build (-DSCINT_COLS_CACHE_BYTES=0.0) takes them at small shapes
+constexpr double kColsCacheBytes = SCINT_COLS_CACHE_BYTES;
 struct TileSlot {
     int inner, col; int64_t batch; bool ok;
 };
@@ -637,7 +641,7 @@ int32_t run_cols_fft(int64_t len, int64_t ncols, int64_t batches, FirstLoader fi
     // beyond it every radix pass is an HBM round trip and the two tiled passes win (16384^2: 5.6
     // vs 7.3 ms).
     const bool beyond_cache =
-        (double)len * (double)ncols * (double)(route_batches > 0 ? route_batches : batches) * 16.0 > 300.0 * 1048576.0;
+        (double)len * (double)ncols * (double)(route_batches > 0 ? route_batches : batches) * 16.0 > kColsCacheBytes;
     if (beyond_cache && len >= 256 && len <= 16384) {
         const int l = ilog2(len), l2 = l / 2, l1 = l - l2;          // L1 >= L2, both in [16, 128]
         const int64_t ntiles = ceil_div(ncols, 16);

@@ -27,9 +27,18 @@ CSRC = os.path.join(REPO, "scintools_amd", "csrc")
 SANITIZE = os.environ.get("SCINT_EMU_SANITIZE", "")
 # SCINT_EMU_DEFINES="-DSCINT_ROWS32=8 ...": extra definitions for the kernel sources (the build constants of csrc/packed.hpp), in a build
 # directory of their own -- to run the interpreter tests on a variant before it is sent to a GPU (tools/build_variant.sh takes the same -D)
+# build(defines=[...]) asks for such a variant by argument: a test module gets its own build (tests/test_fft_tiled_emu_cpu.py:
+# -DSCINT_COLS_CACHE_BYTES=0.0) whatever the environment of the run says, next to the default one in the same process
 DEFINES = os.environ.get("SCINT_EMU_DEFINES", "").split()
-OUT = os.path.join(HERE, "_build" + ("_" + SANITIZE if SANITIZE else "") +
-                   ("_" + "".join(c if c.isalnum() else "_" for c in "".join(DEFINES)) if DEFINES else ""))
+
+
+def out_dir(defines=None):
+    defines = DEFINES if defines is None else list(defines)
+    return os.path.join(HERE, "_build" + ("_" + SANITIZE if SANITIZE else "") +
+                        ("_" + "".join(c if c.isalnum() else "_" for c in "".join(defines)) if defines else ""))
+
+
+OUT = out_dir()
 LIB = os.path.join(OUT, "libscint_emu_test.so")
 
 # same per-unit floating-point contraction as the product build (scintools_amd/build.py)
@@ -52,9 +61,9 @@ def _clang():
     raise RuntimeError("clang++ not found (the kernel sources use clang vector / address-space extensions)")
 
 
-def _stage_sources():
+def _stage_sources(out):
     """Copy csrc into the build directory with the dynamic-LDS declarations rewritten."""
-    src_out = os.path.join(OUT, "scintools_amd", "csrc")
+    src_out = os.path.join(out, "scintools_amd", "csrc")
     os.makedirs(src_out, exist_ok=True)
     changed = False
     for name in sorted(os.listdir(CSRC)):
@@ -78,19 +87,23 @@ def _stage_sources():
             with open(dst, "w") as fh:
                 fh.write(text)
             changed = True
-    inc_out = os.path.join(OUT, "include")
+    inc_out = os.path.join(out, "include")
     os.makedirs(inc_out, exist_ok=True)
     shutil.copy2(os.path.join(REPO, "include", "scint_hip.h"), os.path.join(inc_out, "scint_hip.h"))
     return src_out, changed
 
 
-def build(force=False, verbose=False):
+def build(force=False, verbose=False, defines=None):
+    """Build (if stale) and return the library; `defines` (a list of -D options) instead of SCINT_EMU_DEFINES when given."""
     cxx = _clang()
-    os.makedirs(OUT, exist_ok=True)
-    src_out, _ = _stage_sources()
+    defines = DEFINES if defines is None else list(defines)
+    out = out_dir(defines)
+    lib = os.path.join(out, "libscint_emu_test.so")
+    os.makedirs(out, exist_ok=True)
+    src_out, _ = _stage_sources(out)
     common = [cxx, "-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-fno-omit-frame-pointer",
               "-I", os.path.join(HERE, "include"), "-Wno-unused-result", "-Wno-unknown-attributes",
-              "-Wno-ignored-attributes", "-Wno-unknown-pragmas", "-Wno-pass-failed"] + DEFINES
+              "-Wno-ignored-attributes", "-Wno-unknown-pragmas", "-Wno-pass-failed"] + defines
     link_extra = []
     if SANITIZE:
         common += [f"-fsanitize={SANITIZE}", "-shared-libsan"]
@@ -102,7 +115,7 @@ def build(force=False, verbose=False):
     units.append((os.path.join(HERE, "emu_runtime.cpp"), []))
     units.append((os.path.join(HERE, "emu_selftest.cpp"), []))
     for src, extra in units:
-        obj = os.path.join(OUT, os.path.basename(src) + ".o")
+        obj = os.path.join(out, os.path.basename(src) + ".o")
         objs.append(obj)
         stale = force or not os.path.exists(obj) or any(
             os.path.getmtime(d) > os.path.getmtime(obj) for d in [src] + deps)
@@ -117,12 +130,12 @@ def build(force=False, verbose=False):
             subprocess.run(cmd, check=True)
         with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1)) as pool:
             list(pool.map(run, jobs))
-    if jobs or not os.path.exists(LIB):
-        cmd = [cxx, "-shared", "-fPIC", "-o", LIB] + link_extra + objs + ["-lm", "-lpthread"]
+    if jobs or not os.path.exists(lib):
+        cmd = [cxx, "-shared", "-fPIC", "-o", lib] + link_extra + objs + ["-lm", "-lpthread"]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
-    return LIB
+    return lib
 
 
 def asan_runtime():

@@ -15,23 +15,24 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
-_emu_lib = None
+_emu_libs = {}
 
 
-def load():
-    """Build (if stale) and load the interpreted library with the product's ctypes signatures."""
-    global _emu_lib
-    if _emu_lib is None:
+def load(defines=None):
+    """Build (if stale) and load the interpreted library with the product's ctypes signatures.  `defines`: a list of -D options
+    for a variant build in a directory of its own (build_emu.build), loaded next to the default one."""
+    key = None if defines is None else tuple(defines)
+    if key not in _emu_libs:
         import build_emu
         from scintools_amd import _lib
-        _emu_lib = _lib.bind(ctypes.CDLL(build_emu.build()))
-    return _emu_lib
+        _emu_libs[key] = _lib.bind(ctypes.CDLL(build_emu.build(defines=defines)))
+    return _emu_libs[key]
 
 
-def install(monkeypatch):
+def install(monkeypatch, defines=None):
     import torch
     from scintools_amd import _lib, arcfit, device, dynspec, ththmod
-    lib = load()
+    lib = load(defines)
     cpu = torch.device("cpu")
     monkeypatch.setattr(_lib, "_lib", lib)
     monkeypatch.setattr(_lib, "require_gpu", lambda: lib)

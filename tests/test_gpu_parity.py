@@ -42,6 +42,8 @@ def test_native_library_is_loaded(thth):
 @pytest.mark.parametrize("shape", [(2, 16), (4, 32), (32, 64), (64, 128), (128, 256), (256, 512),
                                    (512, 1024), (1024, 2048), (16, 4096), (8, 8192), (4, 16384),
                                    (2048, 16), (4096, 64), (8192, 32),
+                                   # decimated long rows (n > 8192) at every n1 = 8, 16, 32, few and odd row counts
+                                   (3, 32768), (2, 65536), (5, 131072),
                                    # not powers of two: chirp-z on one or both axes
                                    (2, 1), (3, 5), (7, 16), (16, 7), (75, 101), (128, 96), (96, 128),
                                    (256, 600), (600, 256), (150, 1024), (1000, 30), (30, 5000),
