@@ -58,7 +58,7 @@ extern "C" {
  *   (the VLBI entry points -- scint_cs_complex_batch / scint_vlbi_composite / scint_eigh_top_batch -- and the batched 1-D ACF fit --
  *   scint_acf1d_fit -- and the approximate 2-D one -- scint_acf2d_approx_fit -- and the biharmonic fill -- scint_inpaint_biharmonic --
  *   and the ACFs and secondary spectra of a stack -- scint_acf_batch, scint_sspec_batch -- and the arc fits of a stack --
- *   scint_arc_profile_batch, scint_arc_peak_fit -- only ADD symbols: no bump; a build without them fails at load, which checks every declared symbol) */
+ *   scint_arc_profile_batch, scint_arc_peak_fit -- and the preconditioned biharmonic fill -- scint_inpaint_biharmonic_lines -- only ADD symbols: no bump; a build without them fails at load, which checks every declared symbol) */
 #define SCINT_ABI_VERSION 108
 
 #define SCINT_OK 0
@@ -917,6 +917,26 @@ int32_t scint_inpaint_biharmonic_workspace_bytes(int64_t nf, int64_t nt, int64_t
 int32_t scint_inpaint_biharmonic(double* dyn, int64_t nf, int64_t nt, const uint8_t* mask, int64_t nmask, const double* stencils,
                                  double tol, int32_t max_iter, double* SCINT_HOST residual_out, int32_t* SCINT_HOST iters_out,
                                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* scint_inpaint_biharmonic_lines: the same system, arguments and results as scint_inpaint_biharmonic, solved by PRECONDITIONED
+ *   conjugate gradients.  nchan / nsub = the numbers of channels / sub-integrations whose every pixel is masked (the
+ *   caller counts them: they size the workspace; SCINT_E_ARG if the device finds other numbers).  The preconditioner inverts
+ *   exactly the block of the matrix on the whole channels (a DCT along time, then one symmetric positive definite pentadiagonal
+ *   system per time mode, L D L^T factors formed once per call) and the block on the whole sub-integrations (axes exchanged), and
+ *   divides by the diagonal on the masked pixels in no whole line.  The start is x0 = M^-1 b: for a mask of whole channels only, or
+ *   of whole sub-integrations only, the true residual passes there and *iters_out = 0.  Stopping rule, determinism (no atomics,
+ *   equal inputs give equal bits), errors and the untouched dyn on SCINT_E_NOCONV as above.  A mask without a whole line is
+ *   accepted and gains nothing.  Limits: as above, and an axis that is transformed (time if nchan > 0, frequency if nsub > 0) must
+ *   hold 5 .. 4096 points, or 8192 (SCINT_E_ARG otherwise).  Synchronous.
+ *   Workspace: scint_inpaint_biharmonic_lines_workspace_bytes(nf, nt, nmask, nchan, nsub): 4 nf nt + 60 nmask bytes and 35 KB, plus
+ *   per set of L whole lines of n points 40 L n bytes, and 16 (L + 1) m + 32 n more when n is not a power of two from 16 (m = the
+ *   power of two >= 2 n - 1). */
+int32_t scint_inpaint_biharmonic_lines_workspace_bytes(int64_t nf, int64_t nt, int64_t nmask, int64_t nchan, int64_t nsub,
+                                                       size_t* SCINT_HOST bytes);
+int32_t scint_inpaint_biharmonic_lines(double* dyn, int64_t nf, int64_t nt, const uint8_t* mask, int64_t nmask, int64_t nchan,
+                                       int64_t nsub, const double* stencils, double tol, int32_t max_iter,
+                                       double* SCINT_HOST residual_out, int32_t* SCINT_HOST iters_out, void* workspace,
+                                       size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Scaled-time (NuT) conjugate spectrum: scint_utils.slow_FT (scint_utils.py:655-703).  dyn[nt][nf] is [time][frequency], row-major

@@ -34,6 +34,7 @@ MAX_MODES = 4              # correct_dyn / svd_model; the kernels carry up to 8 
 MEDIAN_MAX_WINDOW = 225    # kf * kt of refill('median') (csrc/clean.hpp, kMedMaxWindow)
 INPAINT_TOL = 1e-12        # = ththmod.DEFAULT_TOL: the true relative residual of the biharmonic fill
 INPAINT_MAX_ITER = 2000    # conjugate-gradient steps of the biharmonic fill (some 50 for isolated pixels and single lines)
+LINES_MAX_LENGTH = 4096    # precond='lines': points of a transformed axis (or twice that: the longest row FFT itself)
 
 _IRREGULAR = ("refill(method={0!r}): only gaps that are whole channels or whole sub-integrations are interpolated on the "
               "device.  For any other mask (isolated pixels, blocks, channels and sub-integrations together) the reference's "
@@ -127,7 +128,7 @@ def stencil_table():
 _STENCILS = None
 
 
-def biharmonic_fill_device(dyn, mask=None, tol=INPAINT_TOL, max_iter=None, info=None):
+def biharmonic_fill_device(dyn, mask=None, tol=INPAINT_TOL, max_iter=None, info=None, precond=None):
     """A copy of the 2-D ``dyn`` with the pixels of ``mask`` (default: the non-finite ones) replaced by the biharmonic fill, the
     method of ``refill(method='biharmonic')`` in the reference (scikit-image's ``inpaint_biharmonic``): with ``L`` the 5-point
     Laplacian with reflecting edges, ``m`` the masked and ``k`` the known pixels, the solution of ``(L L)_mm u_m = -(L L)_mk u_k``
@@ -136,7 +137,20 @@ def biharmonic_fill_device(dyn, mask=None, tol=INPAINT_TOL, max_iter=None, info=
 
     ``max_iter`` (default ``INPAINT_MAX_ITER``) bounds the steps; ``ScintHipError`` when they run out.  The condition number grows
     with the fourth power of the widest gap and the steps with its square root: isolated pixels and single lines take some 50
-    steps, a gap 40 pixels wide will not finish within the default."""
+    steps, a gap 40 pixels wide will not finish within the default.
+
+    ``precond='lines'`` (default ``None``: the route above, unchanged) runs PRECONDITIONED conjugate gradients
+    (``scint_inpaint_biharmonic_lines``): the preconditioner inverts exactly the block of the matrix on the channels whose every
+    pixel is masked (a DCT along time, one pentadiagonal solve per mode) and the block on the wholly masked sub-integrations, and
+    divides by the diagonal elsewhere, so wide bands cost no more steps than narrow ones.  A mask of whole channels only, or of
+    whole sub-integrations only, is solved directly (zero steps).  After a solve ``info`` also receives ``route`` (``'cg'`` without
+    ``precond``; with it ``'direct'`` when no step was needed, else ``'pcg'``) and, with ``precond``, ``line_channels`` and
+    ``line_subints``, the whole lines found (when nothing is masked nothing is solved and ``info`` has none of the three).  Limits: a line with even one known pixel is not whole -- a nearly whole band falls to the diagonal
+    part and stays slow; a mask without any whole line is accepted and gains nothing; an axis that is transformed (time when
+    there are whole channels, frequency when there are whole sub-integrations) must hold 5 .. 4096 points, or 8192
+    (``ValueError`` otherwise).  Errors, and ``dyn`` untouched on failure, as on the plain route."""
+    if precond not in (None, 'lines'):
+        raise ValueError(f"biharmonic_fill_device: precond={precond!r}; None (plain conjugate gradients) or 'lines'")
     out = np.array(dyn, dtype=np.float64)
     if out.ndim != 2:
         raise ValueError("biharmonic_fill_device needs a 2-D array")
@@ -160,15 +174,22 @@ def biharmonic_fill_device(dyn, mask=None, tol=INPAINT_TOL, max_iter=None, info=
     max_iter = INPAINT_MAX_ITER if max_iter is None else int(max_iter)
     if max_iter < 1:
         raise ValueError("biharmonic_fill_device: max_iter must be at least 1")
+    counts = ()
+    if precond == 'lines':
+        counts = (int(np.count_nonzero(bad.all(axis=1))), int(np.count_nonzero(bad.all(axis=0))))
+        for lines, n, axis in ((counts[0], nt, 'time'), (counts[1], nf, 'frequency')):
+            if lines and not lines_length_ok(n):
+                raise ValueError(f"biharmonic_fill_device(precond='lines'): the {axis} axis holds {n} points; the transform along "
+                                 f"it takes 5 .. {LINES_MAX_LENGTH} points, or {2 * LINES_MAX_LENGTH}")
+    entry = "scint_inpaint_biharmonic" if precond is None else "scint_inpaint_biharmonic_lines"
     _lib_ready()
     t = device.to_device(out, torch.float64)
     m = device.to_device(bad, torch.uint8)
     table = device.to_device(stencil_table(), torch.float64)
-    ws = device.workspace_for("scint_inpaint_biharmonic", nf, nt, nmask)
+    ws = device.workspace_for(entry, nf, nt, nmask, *counts)
     residual, iters = ctypes.c_double(), ctypes.c_int32()
     try:
-        _lib.call("scint_inpaint_biharmonic", t, nf, nt, m, nmask, table, tol, max_iter, residual, iters, ws, ws.numel(),
-                  device.stream_ptr())
+        _lib.call(entry, t, nf, nt, m, nmask, *counts, table, tol, max_iter, residual, iters, ws, ws.numel(), device.stream_ptr())
     except _lib.ScintHipError as err:
         if err.status == _lib.SCINT_E_NOCONV:
             noconv = _lib.ScintHipError(f"biharmonic_fill_device: conjugate gradients stopped after {iters.value} steps at a relative "
@@ -179,7 +200,16 @@ def biharmonic_fill_device(dyn, mask=None, tol=INPAINT_TOL, max_iter=None, info=
         raise
     if info is not None:
         info.update(iters=iters.value, residual=residual.value)
+        info.update(route='cg')
+        if precond is not None:
+            info.update(route='pcg' if iters.value else 'direct', line_channels=counts[0], line_subints=counts[1])
     return t.cpu().numpy()
+
+
+def lines_length_ok(n):
+    """Can an axis of ``n`` points be transformed by ``precond='lines'``?  A power of two from 16 runs the row FFT itself (to 8192
+    points), any other length the chirp-z identity at the power of two >= 2 n - 1 (csrc/inpaint.hpp)."""
+    return 5 <= n <= LINES_MAX_LENGTH or n == 2 * LINES_MAX_LENGTH
 
 
 def _start_basis(nt, p):
@@ -318,13 +348,16 @@ def refill(self, method='biharmonic', zeros=True, kernel_size=5, linear=True):
     np.copyto(self.dyn, np.mean(self.dyn[is_valid(self.dyn)]), where=np.isnan(self.dyn))
 
 
-def inpaint(self, zeros=True, tol=INPAINT_TOL):
+def inpaint(self, zeros=True, tol=INPAINT_TOL, precond=None):
     """Replace the non-finite pixels (and with ``zeros`` the zeros, as ``refill`` does) of the dynamic spectrum by the biharmonic
     fill, in place: what the reference's ``refill()`` computes by default where scikit-image is installed.  Any mask is accepted:
-    isolated pixels, blocks, whole channels and sub-integrations together.  See ``biharmonic_fill_device``."""
+    isolated pixels, blocks, whole channels and sub-integrations together.  ``precond='lines'`` fills bands of whole channels or
+    sub-integrations of any width (the default route gives up on gaps some 40 pixels wide).  See ``biharmonic_fill_device``."""
+    if precond not in (None, 'lines'):
+        raise ValueError(f"inpaint: precond={precond!r}; None or 'lines'")
     if zeros:
         np.copyto(self.dyn, np.nan, where=(self.dyn == 0))
-    np.copyto(self.dyn, biharmonic_fill_device(self.dyn, tol=tol))
+    np.copyto(self.dyn, biharmonic_fill_device(self.dyn, tol=tol, precond=precond))
 
 
 def _without_zeros(vec):

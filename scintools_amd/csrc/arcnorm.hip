@@ -9,6 +9,7 @@
 //   scint_zap, scint_refill_median / _linear, scint_svd_model, scint_nanmean_axis, scint_divide_axis
 //                          Dynspec.zap / refill / correct_dyn   dynspec.py:3856-3870, 3273-3410 (kernels: clean.hpp)
 //   scint_inpaint_biharmonic  Dynspec.inpaint: the biharmonic fill of refill   dynspec.py:3301-3307 (kernels: inpaint.hpp)
+//   scint_inpaint_biharmonic_lines  the same fill by preconditioned CG (precond='lines': wide bands of whole lines; inpaint.hpp)
 //
 // Everything here is HBM-bound streaming work (a gather along each delay row, column and row
 // reductions).  Compiled with -ffp-contract=off: the interpolation must round like NumPy's
@@ -785,6 +786,256 @@ extern "C" int32_t scint_inpaint_biharmonic(double* dyn, int64_t nf, int64_t nt,
     if (residual_out) *residual_out = h.bnorm2 > 0.0 ? sqrt(h.true_rho / h.bnorm2) : 0.0;
     if (!ok) { set_error("scint: inpaint_biharmonic: conjugate gradients did not reach the residual"); return SCINT_E_NOCONV; }
     hipLaunchKernelGGL(inpaint_scatter_kernel, dim3(nb), dim3(256), 0, stream, (const double*)x, (const int32_t*)list, n, dyn);
+    SCINT_LAUNCH_CHECK();
+    return SCINT_OK;
+}
+
+// ------------------------------------------------------------------------------
+// biharmonic inpainting with the line-block preconditioner (kernels: inpaint.hpp, second half)
+// ------------------------------------------------------------------------------
+// a line of n points transforms directly when n is a power of two from 16, else by the chirp-z identity at the power of two >= 2 n - 1
+static bool lines_direct(int64_t n) { return is_pow2(n) && n >= 16; }
+static int64_t lines_fft_len(int64_t n) { return lines_direct(n) ? n : std::max<int64_t>(16, next_pow2(2 * n - 1)); }
+static bool lines_len_ok(int64_t n) { return n >= 5 && lines_fft_len(n) <= kLinesMaxFft; }
+
+// the buffers of one set of L whole lines of n points (sizing with ax == nullptr, carving otherwise: one description of the layout)
+static void lines_axis_layout(Carver& carve, int64_t L, int64_t n, int64_t n_across, LineAxis* ax) {
+    const int64_t m = lines_fft_len(n);
+    const bool blue = !lines_direct(n);
+    int32_t* lines = carve.take<int32_t>((size_t)std::max<int64_t>(L, 1));
+    int32_t* pos = carve.take<int32_t>((size_t)n_across);
+    cplx *half = nullptr, *chirp = nullptr, *bhat = nullptr, *buf = nullptr;
+    double *hat = nullptr, *val = nullptr, *fac = nullptr;
+    if (L > 0) {
+        half = carve.take<cplx>((size_t)n);
+        if (blue) {
+            chirp = carve.take<cplx>((size_t)n);
+            bhat = carve.take<cplx>((size_t)m);
+            buf = carve.take<cplx>((size_t)(L * m));
+        }
+        hat = carve.take<double>((size_t)(L * n));
+        val = carve.take<double>((size_t)(L * n));
+        fac = carve.take<double>((size_t)(3 * L * n));
+    }
+    if (ax) {
+        ax->L = (int)L; ax->n = (int)n; ax->m = (int)m; ax->blue = blue; ax->n_across = n_across;
+        ax->lines = lines; ax->pos = pos; ax->half = half; ax->chirp = chirp; ax->bhat = bhat; ax->buf = buf;
+        ax->hat = hat; ax->val = val; ax->fac = fac;
+    }
+}
+
+struct LinesLayout {
+    int32_t *index, *list, *counts, *whole;
+    double *x, *r, *b, *q, *z, *P[2], *part;
+    InpaintLinesState* st;
+    LineAxis ax[2];      // 0: whole channels (lines along time), 1: whole sub-integrations
+    size_t bytes;
+};
+static LinesLayout lines_layout(void* workspace, int64_t nf, int64_t nt, int64_t nmask, int64_t nchan, int64_t nsub, bool carving) {
+    LinesLayout l;
+    const size_t npix = (size_t)nf * (size_t)nt, n = (size_t)std::max<int64_t>(nmask, 1);
+    Carver carve(workspace, ~size_t(0));
+    l.index = carve.take<int32_t>(npix);
+    l.list = carve.take<int32_t>(n);
+    l.counts = carve.take<int32_t>((size_t)ceil_div((int64_t)npix, kInpaintChunk));
+    l.whole = carve.take<int32_t>((size_t)std::max(nf, nt));
+    l.x = carve.take<double>(n); l.r = carve.take<double>(n); l.b = carve.take<double>(n); l.q = carve.take<double>(n);
+    l.z = carve.take<double>(n); l.P[0] = carve.take<double>(n); l.P[1] = carve.take<double>(n);
+    l.part = carve.take<double>((size_t)4 * kCgMaxBlocks);
+    l.st = carve.take<InpaintLinesState>(1);
+    lines_axis_layout(carve, nchan, nt, nf, carving ? &l.ax[0] : nullptr);
+    lines_axis_layout(carve, nsub, nf, nt, carving ? &l.ax[1] : nullptr);
+    l.bytes = align_up(carve.off, 256);
+    return l;
+}
+
+static bool lines_args_ok(int64_t nf, int64_t nt, int64_t nmask, int64_t nchan, int64_t nsub) {
+    return nf >= 1 && nt >= 1 && nf * nt < (int64_t(1) << 31) && nmask >= 0 && nmask <= nf * nt && nchan >= 0 && nchan <= nf &&
+           nsub >= 0 && nsub <= nt;
+}
+
+extern "C" int32_t scint_inpaint_biharmonic_lines_workspace_bytes(int64_t nf, int64_t nt, int64_t nmask, int64_t nchan, int64_t nsub,
+                                                                  size_t* bytes) {
+    SCINT_REQUIRE(bytes && lines_args_ok(nf, nt, nmask, nchan, nsub), "inpaint_biharmonic_lines_workspace_bytes: bad arguments");
+    SCINT_REQUIRE((nchan == 0 || lines_len_ok(nt)) && (nsub == 0 || lines_len_ok(nf)),
+                  "inpaint_biharmonic_lines_workspace_bytes: a transformed axis must hold 5 .. 4096 points, or 8192");
+    *bytes = lines_layout(nullptr, nf, nt, nmask, nchan, nsub, false).bytes;
+    return SCINT_OK;
+}
+
+// the row FFTs of one transform of a set of lines: `values` -> coefficients (forward) or coefficients -> values
+static int32_t lines_transform(const LineAxis& ax, bool forward, const double* r, const int32_t* index, hipStream_t stream) {
+    LinesLoad ld{};
+    ld.n = ax.n; ld.m = ax.m; ld.L = ax.L; ld.blue = ax.blue;
+    ld.src = ax.buf; ld.r = r; ld.index = index; ld.lines = ax.lines; ld.line_stride = ax.line_stride; ld.elem_stride = ax.elem_stride;
+    ld.hat = ax.hat; ld.half = ax.half; ld.chirp = ax.chirp;
+    LinesStore st{};
+    st.n = ax.n; st.m = ax.m; st.blue = ax.blue; st.inv_m = 1.0 / (double)ax.m; st.inv_n = 1.0 / (double)ax.n;
+    st.dst = ax.buf; st.bhat = ax.bhat; st.chirp = ax.chirp; st.half = ax.half; st.hat = ax.hat; st.val = ax.val;
+    ld.mode = forward ? LINES_LD_VALUES : LINES_LD_COEFFS;
+    const int last = forward ? LINES_ST_COEFFS : LINES_ST_VALUES;
+    if (ax.blue) {
+        st.mode = LINES_ST_MULB;
+        const int32_t rc = launch_fft_rows(ax.m, ax.L, ld, st, stream);
+        if (rc != SCINT_OK) return rc;
+        ld.mode = LINES_LD_PLAIN;
+    }
+    st.mode = last;
+    return launch_fft_rows(ax.m, ax.L, ld, st, stream);
+}
+
+extern "C" int32_t scint_inpaint_biharmonic_lines(double* dyn, int64_t nf, int64_t nt, const uint8_t* mask, int64_t nmask,
+                                                  int64_t nchan, int64_t nsub, const double* stencils, double tol, int32_t max_iter,
+                                                  double* residual_out, int32_t* iters_out, void* workspace, size_t workspace_bytes,
+                                                  void* stream_) {
+    SCINT_REQUIRE(dyn && mask && stencils && workspace, "inpaint_biharmonic_lines: null pointer");
+    SCINT_REQUIRE(nf >= 5 && nt >= 5, "inpaint_biharmonic_lines: the 25 stencil classes need nf >= 5 and nt >= 5");
+    SCINT_REQUIRE(lines_args_ok(nf, nt, nmask, nchan, nsub), "inpaint_biharmonic_lines: bad sizes or counts (nf nt < 2^31)");
+    SCINT_REQUIRE(nmask < nf * nt, "inpaint_biharmonic_lines: every pixel is masked");
+    SCINT_REQUIRE(tol > 0.0 && tol < 1.0 && max_iter >= 1, "inpaint_biharmonic_lines: bad tolerance or iteration limit");
+    SCINT_REQUIRE((nchan == 0 || lines_len_ok(nt)) && (nsub == 0 || lines_len_ok(nf)),
+                  "inpaint_biharmonic_lines: a transformed axis must hold 5 .. 4096 points, or 8192");
+    if (residual_out) *residual_out = 0.0;
+    if (iters_out) *iters_out = 0;
+    if (nmask == 0) return SCINT_OK;
+    LinesLayout w = lines_layout(workspace, nf, nt, nmask, nchan, nsub, true);
+    if (workspace_bytes < w.bytes) { set_error("scint: inpaint_biharmonic_lines workspace too small"); return SCINT_E_WORKSPACE; }
+    hipStream_t stream = (hipStream_t)stream_;
+    const int64_t npix = nf * nt, nchunk = ceil_div(npix, kInpaintChunk), n = nmask;
+    const int nb = (int)std::min<int64_t>(kCgMaxBlocks, ceil_div(n, 256));
+    double *RR = w.part, *RZ[2] = {w.part + kCgMaxBlocks, w.part + 2 * kCgMaxBlocks}, *pq = w.part + 3 * kCgMaxBlocks;
+    InpaintLinesState* st = w.st;
+    InpaintLinesState h;
+    w.ax[0].line_stride = nt; w.ax[0].elem_stride = 1;
+    w.ax[1].line_stride = 1; w.ax[1].elem_stride = nt;
+#define SCINT_LINES_READ()                                                                            \
+    do {                                                                                              \
+        SCINT_HIP(hipMemcpyAsync(&h, st, sizeof(InpaintLinesState), hipMemcpyDeviceToHost, stream));  \
+        SCINT_HIP(hipStreamSynchronize(stream));                                                      \
+    } while (0)
+
+    // the unknowns, in pixel order, and the whole lines
+    hipLaunchKernelGGL(inpaint_count_kernel, dim3((unsigned)nchunk), dim3(256), 0, stream, mask, npix, w.counts);
+    SCINT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(inpaint_scan_kernel, dim3(1), dim3(256), 0, stream, w.counts, nchunk, &st->s);
+    SCINT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(inpaint_fill_kernel, dim3((unsigned)nchunk), dim3(256), 0, stream, mask, npix, (const int32_t*)w.counts, n, w.index,
+                       w.list);
+    SCINT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(lines_row_count_kernel, dim3((unsigned)nf), dim3(256), 0, stream, mask, nt, w.whole);
+    SCINT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(lines_list_kernel, dim3(1), dim3(256), 0, stream, (const int32_t*)w.whole, nf, nchan, w.ax[0].pos, w.ax[0].lines,
+                       &st->nlines[0]);
+    SCINT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(lines_col_count_kernel, dim3((unsigned)ceil_div(nt, 256)), dim3(256), 0, stream, mask, nf, nt, w.whole);
+    SCINT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(lines_list_kernel, dim3(1), dim3(256), 0, stream, (const int32_t*)w.whole, nt, nsub, w.ax[1].pos, w.ax[1].lines,
+                       &st->nlines[1]);
+    SCINT_LAUNCH_CHECK();
+    SCINT_LINES_READ();                                 // (before any kernel walks the lists: they are as long as the caller said)
+    SCINT_REQUIRE(h.s.count == n, "inpaint_biharmonic_lines: nmask is not the number of non-zero elements of the mask");
+    SCINT_REQUIRE(h.nlines[0] == nchan && h.nlines[1] == nsub,
+                  "inpaint_biharmonic_lines: nchan / nsub are not the numbers of wholly masked channels / sub-integrations");
+    hipLaunchKernelGGL(inpaint_rhs_kernel, dim3(nb), dim3(256), 0, stream, (const double*)dyn, nf, nt, stencils, (const int32_t*)w.index,
+                       (const int32_t*)w.list, n, w.b, w.r, w.x, RR);
+    SCINT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(inpaint_init_kernel, dim3(1), dim3(256), 0, stream, (const double*)RR, nb, tol, &st->s);
+    SCINT_LAUNCH_CHECK();
+    SCINT_LINES_READ();
+    if (!(h.s.bnorm2 - h.s.bnorm2 == 0.0)) {
+        set_error("scint: inpaint_biharmonic_lines: a known pixel next to a masked one is not finite");
+        return SCINT_E_NONFINITE;
+    }
+    // tables and factors: once per call
+    for (const LineAxis& ax : w.ax) {
+        if (ax.L == 0) continue;
+        hipLaunchKernelGGL(lines_tables_kernel, dim3((unsigned)ceil_div(ax.m, 256)), dim3(256), 0, stream, ax.n, ax.m, ax.blue, ax.half,
+                           ax.chirp, ax.buf);
+        SCINT_LAUNCH_CHECK();
+        if (ax.blue) {
+            LinesLoad ld{};
+            ld.mode = LINES_LD_PLAIN; ld.n = ax.n; ld.m = ax.m; ld.L = 1; ld.src = ax.buf;
+            LinesStore sx{};
+            sx.mode = LINES_ST_PLAIN; sx.n = ax.n; sx.m = ax.m; sx.dst = ax.bhat;
+            const int32_t rc = launch_fft_rows(ax.m, 1, ld, sx, stream);
+            if (rc != SCINT_OK) return rc;
+        }
+        hipLaunchKernelGGL(lines_factor_kernel, dim3((unsigned)ceil_div(ax.n, 256)), dim3(256), 0, stream, (const int32_t*)ax.lines, ax.L,
+                           ax.n_across, ax.n, ax.fac);
+        SCINT_LAUNCH_CHECK();
+    }
+    // out = M^-1 r, partial sums of r.out into `part`
+    auto precondition = [&](double* out, double* part) -> int32_t {
+        for (const LineAxis& ax : w.ax) {
+            if (ax.L == 0) continue;
+            int32_t rc = lines_transform(ax, true, w.r, w.index, stream);
+            if (rc != SCINT_OK) return rc;
+            hipLaunchKernelGGL(lines_solve_kernel, dim3((unsigned)ceil_div(ax.n, 256)), dim3(256), 0, stream, (const double*)ax.fac, ax.L,
+                               ax.n, ax.hat, (const InpaintLinesState*)st);
+            SCINT_LAUNCH_CHECK();
+            rc = lines_transform(ax, false, w.r, w.index, stream);
+            if (rc != SCINT_OK) return rc;
+        }
+        hipLaunchKernelGGL(lines_combine_kernel, dim3(nb), dim3(256), 0, stream, nf, nt, stencils, (const int32_t*)w.list, n,
+                           (const int32_t*)w.ax[0].pos, (const int32_t*)w.ax[1].pos, (const double*)w.ax[0].val,
+                           (const double*)w.ax[1].val, (const double*)w.r, out, part, (const InpaintLinesState*)st);
+        SCINT_LAUNCH_CHECK();
+        return SCINT_OK;
+    };
+    auto true_residual = [&]() -> int32_t {
+        hipLaunchKernelGGL(inpaint_true_kernel, dim3(nb), dim3(256), 0, stream, nf, nt, stencils, (const int32_t*)w.index,
+                           (const int32_t*)w.list, n, (const double*)w.b, (const double*)w.x, w.r, RR, &st->s);
+        SCINT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(inpaint_probe_kernel, dim3(1), dim3(256), 0, stream, (const double*)RR, nb, 1, &st->s);
+        SCINT_LAUNCH_CHECK();
+        SCINT_LINES_READ();
+        return SCINT_OK;
+    };
+    bool ok = h.s.bnorm2 == 0.0;                        // b = 0: the fill is zero
+    int it = 0;
+    if (!ok) {                                          // x0 = M^-1 b: the whole solve when M = A
+        int32_t rc = precondition(w.x, RZ[0]);
+        if (rc != SCINT_OK) return rc;
+        rc = true_residual();
+        if (rc != SCINT_OK) return rc;
+        if (!(h.s.true_rho - h.s.true_rho == 0.0)) { set_error("scint: inpaint_biharmonic_lines: the residual is not finite"); return SCINT_E_NONFINITE; }
+        ok = h.s.done_a != 0;
+    }
+    while (!ok && it < max_iter) {
+        int32_t rc = precondition(w.z, RZ[0]);          // (re)start from the true residual: p = z
+        if (rc != SCINT_OK) return rc;
+        int par = 0, first = 1;
+        do {
+            for (int s = 0; s < kCgCheck && it < max_iter; ++s) {
+                ++it;
+                hipLaunchKernelGGL(lines_ap_kernel, dim3(nb), dim3(256), 0, stream, nf, nt, stencils, (const int32_t*)w.index,
+                                   (const int32_t*)w.list, n, (const double*)w.z, (const double*)w.P[par], w.P[par ^ 1], w.q,
+                                   (const double*)RR, (const double*)RZ[par], (const double*)RZ[par ^ 1], nb, first, it, pq, st);
+                SCINT_LAUNCH_CHECK();
+                hipLaunchKernelGGL(lines_update_kernel, dim3(nb), dim3(256), 0, stream, n, (const double*)w.P[par ^ 1], (const double*)w.q,
+                                   (const double*)pq, nb, w.x, w.r, RR, st);
+                SCINT_LAUNCH_CHECK();
+                rc = precondition(w.z, RZ[par ^ 1]);
+                if (rc != SCINT_OK) return rc;
+                par ^= 1;
+                first = 0;
+            }
+            hipLaunchKernelGGL(inpaint_probe_kernel, dim3(1), dim3(256), 0, stream, (const double*)RR, nb, 0, &st->s);
+            SCINT_LAUNCH_CHECK();
+            SCINT_LINES_READ();
+            if (!(h.s.rho - h.s.rho == 0.0)) { set_error("scint: inpaint_biharmonic_lines: the residual is not finite"); return SCINT_E_NONFINITE; }
+        } while (!h.s.done_a && it < max_iter);
+        // within the bound by the recurrence (or out of steps): the true residual b - A x decides
+        rc = true_residual();
+        if (rc != SCINT_OK) return rc;
+        ok = h.s.done_a != 0;
+        it = h.s.iters;                                 // the steps that did work
+    }
+#undef SCINT_LINES_READ
+    if (iters_out) *iters_out = h.s.bnorm2 > 0.0 ? h.s.iters : 0;
+    if (residual_out) *residual_out = h.s.bnorm2 > 0.0 ? sqrt(h.s.true_rho / h.s.bnorm2) : 0.0;
+    if (!ok) { set_error("scint: inpaint_biharmonic_lines: conjugate gradients did not reach the residual"); return SCINT_E_NOCONV; }
+    hipLaunchKernelGGL(inpaint_scatter_kernel, dim3(nb), dim3(256), 0, stream, (const double*)w.x, (const int32_t*)w.list, n, dyn);
     SCINT_LAUNCH_CHECK();
     return SCINT_OK;
 }
