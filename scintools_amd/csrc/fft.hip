@@ -162,8 +162,8 @@ constexpr int kRedBlocks = 1024;
 
 // Stage 1 of the deterministic reductions.  Every thread keeps four independent running sums
 // (four loads in flight, combined in a fixed order at the end).
-// (The bodies are functions of their own: the kernels of a STACK of problems, further down, run them once per problem -- grid.y --
-// on that problem's values and partials, so a problem's sums are added in the order of the call that takes it alone.)
+// (The bodies are functions of their own: the mean of every problem of a STACK, further down, runs them once per problem -- grid.y --
+// on that problem's values and partials, so a problem's sums are added in the same order whatever the stack holds.)
 template <class F>
 __device__ inline void reduce_partial_body(F f, int64_t n, double* partial, double* red) {
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
@@ -215,9 +215,14 @@ __global__ void __launch_bounds__(256) reduce_final_kernel(const double* partial
 // Both means calc_sspec needs (dynspec.py:3667-3674) in ONE pass over the dynamic spectrum:
 //   m1 = mean(dyn),   m2 = mean(w_f[r] w_t[c] (dyn - m1)) = (S_wd - m1 S_w) / n
 // with S_wd = sum w_f w_t dyn and S_w = sum w_f w_t: three fixed-order sums, then the scalars.
-__device__ inline void sspec_sums_body(const double* __restrict__ dyn, const double* __restrict__ wt,
-                                       const double* __restrict__ wf, int64_t nf, int64_t nt,
-                                       double* partial /*3 x gridDim.x*/, double* red) {
+// dyn[B][nf][nt] is a stack of problems (one problem: grid.y = 1): problem blockIdx.y has its partials 3 * gridDim.x apart and its
+// two means at scal[2 b], scal[2 b + 1]; grid.x depends on nf alone, so a problem's sums are added in the same order whatever B is.
+__global__ void __launch_bounds__(256) sspec_sums_kernel(const double* __restrict__ dyn, const double* __restrict__ wt,
+                                                         const double* __restrict__ wf, int64_t nf, int64_t nt,
+                                                         double* partial /*B x 3 x gridDim.x*/) {
+    __shared__ double red[4];
+    dyn += (int64_t)blockIdx.y * nf * nt;
+    partial += (int64_t)blockIdx.y * 3 * gridDim.x;
     double sd = 0.0, swd = 0.0, sw = 0.0;
     for (int64_t r = blockIdx.x; r < nf; r += gridDim.x) {
         const double fr = wf ? wf[r] : 1.0;
@@ -233,13 +238,10 @@ __device__ inline void sspec_sums_body(const double* __restrict__ dyn, const dou
         partial[blockIdx.x] = sd; partial[gridDim.x + blockIdx.x] = swd; partial[2 * gridDim.x + blockIdx.x] = sw;
     }
 }
-__global__ void __launch_bounds__(256) sspec_sums_kernel(const double* __restrict__ dyn, const double* __restrict__ wt,
-                                                         const double* __restrict__ wf, int64_t nf, int64_t nt,
-                                                         double* partial /*3 x gridDim.x*/) {
+__global__ void __launch_bounds__(256) sspec_means_kernel(const double* partial, int np, double n, double* scal) {
     __shared__ double red[4];
-    sspec_sums_body(dyn, wt, wf, nf, nt, partial, red);
-}
-__device__ inline void sspec_means_body(const double* partial, int np, double n, double* scal, double* red) {
+    partial += (int64_t)blockIdx.y * 3 * np;
+    scal += 2 * blockIdx.y;
     double sd = 0.0, swd = 0.0, sw = 0.0;
     for (int i = threadIdx.x; i < np; i += 256) { sd += partial[i]; swd += partial[np + i]; sw += partial[2 * np + i]; }
     sd = block_sum(sd, red); swd = block_sum(swd, red); sw = block_sum(sw, red);
@@ -249,25 +251,9 @@ __device__ inline void sspec_means_body(const double* partial, int np, double n,
         scal[1] = (swd - m1 * sw) / n;
     }
 }
-__global__ void __launch_bounds__(256) sspec_means_kernel(const double* partial, int np, double n, double* scal) {
-    __shared__ double red[4];
-    sspec_means_body(partial, np, n, scal, red);
-}
-// The same for a stack dyn[B][nf][nt]: problem blockIdx.y with the single problem's grid.x, its partials 3 * gridDim.x apart, its two
-// means at scal[2 b], scal[2 b + 1] -- the sums of a problem are added in the order of the call that takes it alone.
-__global__ void __launch_bounds__(256) sspec_stack_sums_kernel(const double* __restrict__ dyn, const double* __restrict__ wt,
-                                                               const double* __restrict__ wf, int64_t nf, int64_t nt,
-                                                               double* partial /*B x 3 x gridDim.x*/) {
-    __shared__ double red[4];
-    sspec_sums_body(dyn + (int64_t)blockIdx.y * nf * nt, wt, wf, nf, nt, partial + (int64_t)blockIdx.y * 3 * gridDim.x, red);
-}
-__global__ void __launch_bounds__(256) sspec_stack_means_kernel(const double* partial, int np, double n, double* scal) {
-    __shared__ double red[4];
-    sspec_means_body(partial + (int64_t)blockIdx.y * 3 * np, np, n, scal + 2 * blockIdx.y, red);
-}
 
-// workgroups of a two-stage reduction over n values: a sum (launch_reduce) and the maximum of an ACF.  The stack kernels use
-// the same counts, which is what gives a problem of a stack the partials -- and the bits -- of the single call.
+// workgroups (grid.x) of a two-stage reduction over a problem's n values: a sum and the maximum of an ACF.  They depend on the
+// problem's size alone, never on how many problems a stack holds: a problem has the same partials -- and bits -- alone and in a stack.
 static int reduce_blocks(int64_t n) { return (int)std::min<int64_t>(kRedBlocks, std::max<int64_t>(1, ceil_div(n, 256 * 4))); }
 static int max_blocks(int64_t n) { return (int)std::min<int64_t>(kRedBlocks, std::max<int64_t>(1, ceil_div(n, 1024))); }
 static int sspec_sums_blocks(int64_t nf) { return (int)std::min<int64_t>(kRedBlocks, nf); }
@@ -347,8 +333,7 @@ __device__ inline int shift_half(int i, int n) {
 }
 
 enum SrcMode { SRC_ARRAY = 0, SRC_SSPEC = 1, SRC_CS = 2, SRC_MODEL = 3, SRC_MULCONJ = 4, SRC_CONJ = 5,
-               SRC_ACF_IN = 6, SRC_POWER = 7, SRC_CPAD = 8, SRC_DBPOWER = 9, SRC_ROLL = 10,
-               SRC_SSPEC_STACK = 11 };
+               SRC_ACF_IN = 6, SRC_POWER = 7, SRC_CPAD = 8, SRC_DBPOWER = 9, SRC_ROLL = 10 };
 
 // Element (row, j) of the row-FFT input, j in [0, fft length).
 struct RowSource {
@@ -357,8 +342,8 @@ struct RowSource {
     const cplx* chirp;   // optional: multiply element j < n_in by chirp[j]
     // SRC_ARRAY: a[row*ld + j];  SRC_MULCONJ: conj(a[row*ld + j] * b[j])
     const cplx* a; int ld; const cplx* b;
-    // SRC_SSPEC (dynspec.py:3667-3685)
-    WindowedValue wv; const double* m2; int nt_eff; int prewhite;
+    // SRC_SSPEC (dynspec.py:3667-3685): the two means are wv.m1[0] and wv.m1[1]
+    WindowedValue wv; int nt_eff; int prewhite;
     // SRC_CS: np.pad(dspec, right, constant)  (ththmod.py:777-782): reuses wv.dyn / wv.nt
     // SRC_CPAD: np.pad(x, right, 0) of a COMPLEX x[., wv.nt] = a (a visibility, ththmod.py:1313-1321): reuses a / wv.nt
     double pad;
@@ -368,15 +353,14 @@ struct RowSource {
     // SRC_ROLL: x[(r + roll_r) % R][(j + roll_c) % C] of a real x = wv.dyn (roll_real) or a complex x = a: fftshift is a roll by
     // n - n/2, ifftshift one by n/2 -- they differ on odd lengths (scint_fft2_any)
     int roll_r, roll_c, roll_real;
-    // SRC_ACF_IN on a stack of problems (rows b * prob_rows + r of wv.dyn are problem b's): the mean of row r is
-    // wv.m1[r / prob_rows]; 0: one problem, wv.m1[0].  (SRC_POWER needs no more than the stacked rows: it has no scalar.)
+    // SRC_ACF_IN and SRC_SSPEC serve one problem and a stack of problems alike.  prob_rows == 0: one problem, whose scalars are at
+    // wv.m1 -- no decode (SRC_SSPEC's own instantiation, which with_source gives one problem, does not even hold the branch).
+    // prob_rows > 0, a wave-uniform branch: the rows of a stack, row r being row r % prob_rows of problem
+    // b = r / prob_rows.  SRC_ACF_IN: rows b * prob_rows + r of wv.dyn are problem b's, its mean is wv.m1[b].  SRC_SSPEC: the stack is
+    // wv.dyn[B][prob_rows + prewhite][wv.nt] (under prewhitening a problem has one row more to read than to transform: the stencil
+    // reads one row further, inside the problem), the problem's two means are wv.m1[2 b] and wv.m1[2 b + 1], the windows are shared.
+    // (SRC_POWER needs no more than the stacked rows: it has no scalar.)
     int prob_rows;
-    // SRC_SSPEC_STACK: SRC_SSPEC of a stack wv.dyn[B][prob_src_rows][wv.nt].  Row r is row r % prob_rows of problem b = r / prob_rows
-    // (prob_rows = prob_src_rows - 1 under prewhitening: the stencil reads one row further, inside the problem); the problem's
-    // two means are wv.m1[2 b] and wv.m1[2 b + 1], the windows are shared.  The arithmetic on a value is SRC_SSPEC's.
-    int prob_src_rows;
-
-    __device__ inline double sspec_d(int r, int c) const { return wv.at(r, c) - m2[0]; }
 
     template <int M = -1>
     __device__ inline cplx get(int r, int j) const {
@@ -398,22 +382,21 @@ struct RowSource {
             case SRC_DBPOWER:  // -inf dB (an exact zero of power) gives pow(10, -inf) = 0
                 v = mk(pow(10.0, wv.dyn[(int64_t)shift_half(r, R) * C + shift_half(j, C)] / 10.0), 0.0);
                 break;
-            case SRC_SSPEC:
-                if (j >= nt_eff) v = mk(0.0, 0.0);
-                else if (!prewhite) v = mk(sspec_d(r, j), 0.0);
-                else  // convolve2d([[1,-1],[-1,1]], dyn, 'valid')  (dynspec.py:3681)
-                    v = mk(sspec_d(r + 1, j + 1) - sspec_d(r + 1, j) - sspec_d(r, j + 1) + sspec_d(r, j), 0.0);
-                break;
-            case SRC_SSPEC_STACK: {
-                const int pb = r / prob_rows, rr = r - pb * prob_rows;
+            case SRC_SSPEC: {
                 WindowedValue w = wv;
-                w.dyn += (int64_t)pb * prob_src_rows * wv.nt;
-                w.m1 += 2 * pb;
+                int rr = r;
+                if (M < 0 && prob_rows > 0) {       // (M >= 0: with_source's instantiation, taken for one problem only)
+                    const int pb = r / prob_rows;
+                    rr = r - pb * prob_rows;
+                    w.dyn += (int64_t)pb * (prob_rows + (prewhite ? 1 : 0)) * wv.nt;
+                    w.m1 += 2 * pb;
+                }
                 const double mean2 = w.m1[1];
                 auto d = [&](int a, int c) { return w.at(a, c) - mean2; };
                 if (j >= nt_eff) v = mk(0.0, 0.0);
                 else if (!prewhite) v = mk(d(rr, j), 0.0);
-                else v = mk(d(rr + 1, j + 1) - d(rr + 1, j) - d(rr, j + 1) + d(rr, j), 0.0);
+                else  // convolve2d([[1,-1],[-1,1]], dyn, 'valid')  (dynspec.py:3681)
+                    v = mk(d(rr + 1, j + 1) - d(rr + 1, j) - d(rr, j + 1) + d(rr, j), 0.0);
                 break;
             }
             case SRC_CS: v = mk(j < wv.nt ? wv.dyn[(int64_t)r * wv.nt + j] : pad, 0.0); break;
@@ -436,14 +419,24 @@ struct RowSource {
     }
     __device__ inline cplx operator()(int r, int j) const { return get<-1>(r, j); }
 };
+template <class F>
+static int32_t with_source(const RowSource& s, F&& f);
+// get<M> holds no problem decode, so a RowSourceM may only wrap a source of ONE problem: with_source, which checks that, is the
+// only code that can construct one
 template <int M>
 struct RowSourceM {
-    RowSource s;
     __device__ inline cplx operator()(int r, int j) const { return s.template get<M>(r, j); }
+private:
+    RowSource s;
+    explicit RowSourceM(const RowSource& one_problem) : s(one_problem) {}
+    template <class F>
+    friend int32_t with_source(const RowSource& s, F&& f);
 };
-// f(source functor): the hot modes get their own instantiation
+// f(source functor): the hot modes of ONE problem get their own instantiation, which holds no problem decode at all;
+// a stacked source keeps the run-time functor and its wave-uniform prob_rows branch
 template <class F>
 static int32_t with_source(const RowSource& s, F&& f) {
+    if (s.prob_rows > 0) return f(s);
     switch (s.mode) {
         case SRC_SSPEC: return f(RowSourceM<SRC_SSPEC>{s});
         case SRC_CS: return f(RowSourceM<SRC_CS>{s});
@@ -969,7 +962,7 @@ static int32_t fft2_general(RowSource src, int64_t nvalid, double fill0, int64_t
         src.chirp = ch->w;
         rc = rows_fft_pow2(src, nrows, p.mC, rowA, p.mC, stream);
         if (rc != SCINT_OK) return rc;
-        RowSource s2;
+        RowSource s2{};
         s2.mode = SRC_MULCONJ; s2.n_in = (int)p.mC; s2.chirp = nullptr;
         s2.a = rowA; s2.ld = (int)p.mC; s2.b = ch->B;
         rc = rows_fft_pow2(s2, nrows, p.mC, rowB, p.mC, stream);
@@ -1225,6 +1218,39 @@ extern "C" int32_t scint_sspec_workspace_bytes(int64_t nf, int64_t nt, size_t* b
     return SCINT_OK;
 }
 
+// The generic (fft2_general) route of the secondary spectrum, written once for a stack [B][nf][nt]; scint_sspec is its B = 1.
+// The two means of every problem (2 launches, grid.y = B), the row pass over the stacked rows, the column passes with the problem
+// as grid.z: launches do not grow with B.  B = 1 means one problem to every kernel: grid.y = 1 in the reductions, a source that
+// decodes no problem (prob_rows = 0) and fft2_general's one-problem kernels (stack = 0).  A problem of a larger stack gets the
+// same sums in the same order and the same expressions on its values, hence the same bits.
+// The carve is scint_sspec_batch_workspace_bytes' own sum.  One problem's also fits scint_sspec_workspace_bytes, whose value is ABI
+// and older than this layout: after the transform's buffers (rounded up by at most 255 bytes) it takes at most 3 * kRedBlocks
+// partials and 2 means, 24576 + 16 bytes, of the 8 * (3 * kRedBlocks + 8) + 2048 = 26688 bytes that size adds to them.
+static int32_t sspec_generic(const double* stack, int64_t B, int64_t nf, int64_t nt, const double* win_t, const double* win_f,
+                             int32_t prewhite, int32_t halve, const double* pd_fd, const double* pd_td, double* sec_out,
+                             void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    const int64_t R = 2 * next_pow2(nf), C = 2 * next_pow2(nt);  // dynspec.py:3677-3678
+    const size_t fft_bytes = align_up(fft2_general_ws(R, C, nf, B), 256);
+    Carver cv((char*)workspace + fft_bytes, workspace_bytes - fft_bytes);
+    const int blocks = sspec_sums_blocks(nf);
+    double* partial = cv.take<double>(3 * (size_t)B * (size_t)blocks);
+    double* scal = cv.take<double>(2 * (size_t)B);   // [2 b] = mean1, [2 b + 1] = mean2 of problem b
+    if (!cv.ok()) { set_error("scint: sspec workspace too small for the means of the generic route"); return SCINT_E_WORKSPACE; }
+    hipLaunchKernelGGL(sspec_sums_kernel, dim3(blocks, (unsigned)B), dim3(256), 0, stream, stack, win_t, win_f, nf, nt, partial);
+    hipLaunchKernelGGL(sspec_means_kernel, dim3(1, (unsigned)B), dim3(256), 0, stream, (const double*)partial, blocks,
+                       (double)(nf * nt), scal);
+    SCINT_LAUNCH_CHECK();
+    const int64_t nf_eff = prewhite ? nf - 1 : nf, nt_eff = prewhite ? nt - 1 : nt;
+    RowSource src{};
+    src.mode = SRC_SSPEC; src.wv = WindowedValue{stack, win_t, win_f, scal, (int)nt};
+    src.nt_eff = nt_eff; src.prewhite = prewhite; src.prob_rows = B > 1 ? (int)nf_eff : 0;
+    ColSink sink{};
+    sink.mode = SINK_SSPEC; sink.out_d = sec_out; sink.halve = halve; sink.prewhite = prewhite;
+    sink.pd_fd = pd_fd; sink.pd_td = pd_td;
+    return fft2_general(src, nf_eff, 0.0, R, C, sink, workspace, fft_bytes, stream, /*real_input=*/true, B > 1 ? B : 0,
+                        (halve ? R / 2 : R) * C);
+}
+
 extern "C" int32_t scint_sspec(const double* dyn, int64_t nf, int64_t nt, const double* win_t,
                                const double* win_f, int32_t prewhite, int32_t halve,
                                const double* pd_fd, const double* pd_td, double* sec_out,
@@ -1238,40 +1264,20 @@ extern "C" int32_t scint_sspec(const double* dyn, int64_t nf, int64_t nt, const 
     size_t need = 0;
     scint_sspec_workspace_bytes(nf, nt, &need);
     if (workspace_bytes < need) { set_error("scint: sspec workspace too small"); return SCINT_E_WORKSPACE; }
-    const int64_t R = 2 * next_pow2(nf), C = 2 * next_pow2(nt);  // dynspec.py:3677-3678
-    SCINT_REQUIRE(C >= 16, "sspec: nt must be at least 5");
+    SCINT_REQUIRE(2 * next_pow2(nt) >= 16, "sspec: nt must be at least 5");
     if (sspec_fast_supported(nf, nt, halve))      // two HBM round trips instead of four (sspec.hip)
         return sspec_fast(dyn, nf, nt, win_t, win_f, prewhite, pd_fd, pd_td, sec_out, workspace, stream);
-    const size_t fft_bytes = fft2_general_ws(R, C, nf);
-    Carver cv((char*)workspace + align_up(fft_bytes, 256), workspace_bytes - align_up(fft_bytes, 256));
-    double* partial = cv.take<double>(3 * kRedBlocks);
-    double* scal = cv.take<double>(8);  // [0] = mean1, [1] = mean2
-
-    {
-        const int blocks = sspec_sums_blocks(nf);
-        hipLaunchKernelGGL(sspec_sums_kernel, dim3(blocks), dim3(256), 0, stream, dyn, win_t, win_f, nf, nt, partial);
-        hipLaunchKernelGGL(sspec_means_kernel, dim3(1), dim3(256), 0, stream, partial, blocks, (double)(nf * nt), scal);
-        SCINT_LAUNCH_CHECK();
-    }
-    WindowedValue wv{dyn, win_t, win_f, scal, (int)nt};
-    const int64_t nf_eff = prewhite ? nf - 1 : nf, nt_eff = prewhite ? nt - 1 : nt;
-    RowSource src{};
-    src.mode = SRC_SSPEC; src.wv = wv; src.m2 = scal + 1; src.nt_eff = nt_eff; src.prewhite = prewhite;
-    ColSink sink{};
-    sink.mode = SINK_SSPEC; sink.out_d = sec_out; sink.halve = halve; sink.prewhite = prewhite;
-    sink.pd_fd = pd_fd; sink.pd_td = pd_td;
-    return fft2_general(src, nf_eff, 0.0, R, C, sink, workspace, fft_bytes, stream, /*real_input=*/true);
+    return sspec_generic(dyn, 1, nf, nt, win_t, win_f, prewhite, halve, pd_fd, pd_td, sec_out, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------
 // scint_sspec_batch: scint_sspec of every problem of a stack [B][nf][nt]
 // ------------------------------------------------------------------------------
 // Segments whose padded half-lengths are below 256 on either axis (up to 128 channels or 128 sub-integrations) -- the ones a cut
-// into many segments makes -- take scint_sspec's fft2_general route as a stack: the two means per problem (2 launches, grid.y),
-// the row pass over the stacked rows, the column passes with the problem as grid.z; launches do not grow with B.  Larger ones
-// take scint_sspec's persistent kernels (sspec.hip), which have no problem index: they run problem after problem on one
-// problem's workspace, so their launches DO grow with B (a cut leaves few segments of that size).  Either way out[b] has the
-// bits of scint_sspec on stack[b].
+// into many segments makes -- take the generic route, sspec_generic above: the one scint_sspec takes with B = 1, so there is no
+// second copy to keep in step; launches do not grow with B.  Larger ones take scint_sspec's persistent kernels (sspec.hip), which
+// have no problem index: they run problem after problem on one problem's workspace, so their launches DO grow with B (a cut
+// leaves few segments of that size).  Either way out[b] has the bits of scint_sspec on stack[b].
 namespace scint {
 static bool sspec_batch_shape_ok(int64_t B, int64_t nf, int64_t nt) {
     return B >= 1 && B <= 65535 && nf >= 2 && nt >= 2 && nf < (1 << 22) && nt < (1 << 22) && B * 2 * next_pow2(nf) < (1 << 30) &&
@@ -1312,23 +1318,7 @@ extern "C" int32_t scint_sspec_batch(const double* stack, int64_t B, int64_t nf,
         }
         return SCINT_OK;
     }
-    const size_t fft_bytes = align_up(fft2_general_ws(R, C, nf, B), 256);
-    Carver cv((char*)workspace + fft_bytes, workspace_bytes - fft_bytes);
-    const int blocks = sspec_sums_blocks(nf);
-    double* partial = cv.take<double>(3 * (size_t)B * (size_t)blocks);
-    double* scal = cv.take<double>(2 * (size_t)B);   // [2 b] = mean1, [2 b + 1] = mean2 of problem b
-    hipLaunchKernelGGL(sspec_stack_sums_kernel, dim3(blocks, (unsigned)B), dim3(256), 0, stream, stack, win_t, win_f, nf, nt, partial);
-    hipLaunchKernelGGL(sspec_stack_means_kernel, dim3(1, (unsigned)B), dim3(256), 0, stream, (const double*)partial, blocks,
-                       (double)(nf * nt), scal);
-    SCINT_LAUNCH_CHECK();
-    const int64_t nf_eff = prewhite ? nf - 1 : nf, nt_eff = prewhite ? nt - 1 : nt;
-    RowSource src{};
-    src.mode = SRC_SSPEC_STACK; src.wv = WindowedValue{stack, win_t, win_f, scal, (int)nt};
-    src.nt_eff = nt_eff; src.prewhite = prewhite; src.prob_rows = (int)nf_eff; src.prob_src_rows = (int)nf;
-    ColSink sink{};
-    sink.mode = SINK_SSPEC; sink.out_d = sec_out; sink.halve = halve; sink.prewhite = prewhite;
-    sink.pd_fd = pd_fd; sink.pd_td = pd_td;
-    return fft2_general(src, nf_eff, 0.0, R, C, sink, workspace, fft_bytes, stream, /*real_input=*/true, B, out_stride);
+    return sspec_generic(stack, B, nf, nt, win_t, win_f, prewhite, halve, pd_fd, pd_td, sec_out, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------
@@ -1493,36 +1483,8 @@ extern "C" int32_t scint_gerchberg_saxton(scint_c128* wavefield, int64_t rows, i
 // scint_acf: Dynspec.calc_acf(method='direct') (dynspec.py:3780-3797)
 // ------------------------------------------------------------------------------
 namespace scint {
-struct MaxAbsValue {   // arr /= np.max(arr): the maximum of a real array via two-stage max
-    const double* x;
-};
-__device__ inline void max_partial_body(const double* x, int64_t n, double* partial, double* red) {
-    double m = -INFINITY;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        m = fmax(m, x[i]);
-    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
-__global__ void __launch_bounds__(256) max_partial_kernel(const double* x, int64_t n, double* partial) {
-    __shared__ double red[4];
-    max_partial_body(x, n, partial, red);
-}
-__device__ inline void scale_by_max_body(double* x, int64_t n, const double* partial, int np) {
-    double m = -INFINITY;
-    for (int i = 0; i < np; ++i) m = fmax(m, partial[i]);
-    const double inv = 1.0 / m;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        x[i] = x[i] / m;
-    (void)inv;
-}
-__global__ void __launch_bounds__(256) scale_by_max_kernel(double* x, int64_t n, const double* partial, int np) {
-    scale_by_max_body(x, n, partial, np);
-}
-
-// The reductions of a stack x[B][n]: problem blockIdx.y runs the single problem's body with the single problem's grid.x on its own
-// values, partials (gridDim.x of them) and result -- its mean and its maximum have the bits of the call that takes it alone.
+// The reductions of a stack x[B][n] (one problem: grid.y = 1): problem blockIdx.y works with a grid.x that depends on n alone on its
+// own values, partials (gridDim.x of them) and result, so its mean and its maximum have the same bits alone and in any stack.
 __global__ void __launch_bounds__(256) stack_sum_partial_kernel(const double* x, int64_t n, double* partial) {
     __shared__ double red[4];
     reduce_partial_body(PlainValue{x + (int64_t)blockIdx.y * n}, n, partial + (int64_t)blockIdx.y * gridDim.x, red);
@@ -1531,12 +1493,81 @@ __global__ void __launch_bounds__(256) stack_sum_final_kernel(const double* part
     __shared__ double red[4];
     reduce_final_body(partial + (int64_t)blockIdx.y * np, np, scale, out + blockIdx.y, red);
 }
-__global__ void __launch_bounds__(256) stack_max_partial_kernel(const double* x, int64_t n, double* partial) {
+// arr /= np.max(arr): the maximum of a real array via two-stage max, then the division
+__global__ void __launch_bounds__(256) max_partial_kernel(const double* x, int64_t n, double* partial) {
     __shared__ double red[4];
-    max_partial_body(x + (int64_t)blockIdx.y * n, n, partial + (int64_t)blockIdx.y * gridDim.x, red);
+    x += (int64_t)blockIdx.y * n;
+    partial += (int64_t)blockIdx.y * gridDim.x;
+    double m = -INFINITY;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        m = fmax(m, x[i]);
+    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
 }
-__global__ void __launch_bounds__(256) stack_scale_by_max_kernel(double* x, int64_t n, const double* partial, int np) {
-    scale_by_max_body(x + (int64_t)blockIdx.y * n, n, partial + (int64_t)blockIdx.y * np, np);
+__global__ void __launch_bounds__(256) scale_by_max_kernel(double* x, int64_t n, const double* partial, int np) {
+    x += (int64_t)blockIdx.y * n;
+    partial += (int64_t)blockIdx.y * np;
+    double m = -INFINITY;
+    for (int i = 0; i < np; ++i) m = fmax(m, partial[i]);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        x[i] = x[i] / m;
+}
+// both on B arrays of n values each, after the call that wrote them
+static int32_t normalise_by_max(double* x, int64_t B, int64_t n, double* partial /*B x max_blocks(n)*/, hipStream_t stream) {
+    const int blocks = max_blocks(n);
+    hipLaunchKernelGGL(max_partial_kernel, dim3(blocks, (unsigned)B), dim3(256), 0, stream, (const double*)x, n, partial);
+    hipLaunchKernelGGL(scale_by_max_kernel, dim3(blocks, (unsigned)B), dim3(256), 0, stream, x, n, (const double*)partial, blocks);
+    SCINT_LAUNCH_CHECK();
+    return SCINT_OK;
+}
+
+// scint_acf and scint_acf_batch: the direct ACF, written once for a stack [B][nf][nt]; scint_acf is its B = 1.
+// Per group of B problems: the means (2 launches, or a memset), the forward transform, the transform of the power, the maxima
+// and the division (2 launches) -- fft2_general's row and column passes with the problem as a range of slots / grid.z, so the
+// launches do not grow with B.  B = 1 means one problem to every kernel: grid.y = 1 in the reductions, a source that decodes no
+// problem (prob_rows = 0) and fft2_general's one-problem kernels (stack = 0).  A problem of a larger stack gets the same sums and
+// maxima in the same order and the same transforms, hence the same bits.
+// Moved per problem: 8 nf nt read; the complex intermediates (the row pass's result and the column working array of both
+// transforms, and the spectrum between them) written and read once each, 16 * 2nf * 2nt bytes apiece at power-of-two
+// lengths; 8 * 4 nf nt written, and read and written once more by the normalisation.
+// The carve is scint_acf_batch_workspace_bytes' own sum.  One problem's also fits scint_acf_workspace_bytes, whose value is ABI
+// and older than this layout: after the transform's buffers (rounded up by at most 255 bytes) it takes the spectrum (a multiple of
+// 64 bytes: rounded up by at most 192), at most kRedBlocks partials and 1 mean, 192 + 8192 + 8 bytes beyond the spectrum, of the
+// 8 * (kRedBlocks + 8) + 1024 = 9280 bytes that size adds to the two.
+static int32_t acf_stack(const double* stack, int64_t B, int64_t nf, int64_t nt, int32_t subtract_mean, int32_t normalise,
+                         double* acf_out, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    const int64_t R = 2 * nf, C = 2 * nt, fft_stack = B > 1 ? B : 0;
+    const size_t fft_bytes = align_up(fft2_general_ws(R, C, R, B), 256);
+    Carver cv((char*)workspace + fft_bytes, workspace_bytes - fft_bytes);
+    cplx* spec = cv.take<cplx>((size_t)B * (size_t)R * (size_t)C);
+    double* partial = cv.take<double>((size_t)B * (size_t)max_blocks(R * C));      // (>= the mean's: R C = 4 nf nt)
+    double* scal = cv.take<double>((size_t)B);
+    if (!cv.ok()) { set_error("scint: acf workspace too small for the spectrum and the reductions"); return SCINT_E_WORKSPACE; }
+    if (subtract_mean) {
+        const int blocks = reduce_blocks(nf * nt);
+        hipLaunchKernelGGL(stack_sum_partial_kernel, dim3(blocks, (unsigned)B), dim3(256), 0, stream, stack, nf * nt, partial);
+        hipLaunchKernelGGL(stack_sum_final_kernel, dim3(1, (unsigned)B), dim3(256), 0, stream, (const double*)partial, blocks,
+                           1.0 / (double)(nf * nt), scal);
+        SCINT_LAUNCH_CHECK();
+    } else {
+        SCINT_HIP(hipMemsetAsync(scal, 0, sizeof(double) * (size_t)B, stream));
+    }
+    RowSource f{};
+    f.mode = SRC_ACF_IN; f.wv.dyn = stack; f.wv.nt = nt; f.wv.m1 = scal; f.prob_rows = B > 1 ? (int)nf : 0;
+    ColSink fs{};
+    fs.mode = SINK_ARRAY; fs.out_c = spec; fs.ld = C;
+    int32_t rc = fft2_general(f, nf, 0.0, R, C, fs, workspace, fft_bytes, stream, /*real_input=*/true, fft_stack, R * C);
+    if (rc != SCINT_OK) return rc;
+    RowSource b{};
+    b.mode = SRC_POWER; b.a = spec; b.ld = C;
+    ColSink bs{};
+    bs.mode = SINK_ACF; bs.out_d = acf_out; bs.scale = 1.0 / ((double)R * (double)C);
+    // the power spectrum is real and even, so fft2 and ifft2 of it coincide up to the 1/(RC) factor
+    rc = fft2_general(b, R, 0.0, R, C, bs, workspace, fft_bytes, stream, /*real_input=*/true, fft_stack, R * C);
+    if (rc != SCINT_OK || !normalise) return rc;
+    return normalise_by_max(acf_out, B, R * C, partial, stream);
 }
 }  // namespace scint
 
@@ -1555,46 +1586,14 @@ extern "C" int32_t scint_acf(const double* dyn, int64_t nf, int64_t nt, int32_t 
     size_t need = 0;
     scint_acf_workspace_bytes(nf, nt, &need);
     if (workspace_bytes < need) { set_error("scint: acf workspace too small"); return SCINT_E_WORKSPACE; }
-    hipStream_t stream = (hipStream_t)stream_;
-    const int64_t R = 2 * nf, C = 2 * nt;
-    const size_t fft_bytes = align_up(fft2_general_ws(R, C, R), 256);
-    cplx* spec = (cplx*)((char*)workspace + fft_bytes);
-    Carver cv((char*)workspace + fft_bytes + sizeof(cplx) * (size_t)R * (size_t)C,
-              workspace_bytes - fft_bytes - sizeof(cplx) * (size_t)R * (size_t)C);
-    double* partial = cv.take<double>(kRedBlocks);
-    double* scal = cv.take<double>(8);
-    int32_t rc = SCINT_OK;
-    if (subtract_mean) rc = launch_reduce(PlainValue{dyn}, nf * nt, 1.0 / (double)(nf * nt), partial, scal, stream);
-    else SCINT_HIP(hipMemsetAsync(scal, 0, sizeof(double), stream));
-    if (rc != SCINT_OK) return rc;
-    RowSource f{};
-    f.mode = SRC_ACF_IN; f.wv.dyn = dyn; f.wv.nt = nt; f.wv.m1 = scal;
-    ColSink fs{};
-    fs.mode = SINK_ARRAY; fs.out_c = spec; fs.ld = C;
-    rc = fft2_general(f, nf, 0.0, R, C, fs, workspace, fft_bytes, stream, /*real_input=*/true);
-    if (rc != SCINT_OK) return rc;
-    RowSource b{};
-    b.mode = SRC_POWER; b.a = spec; b.ld = C;
-    ColSink bs{};
-    bs.mode = SINK_ACF; bs.out_d = acf_out; bs.scale = 1.0 / ((double)R * (double)C);
-    // the power spectrum is real and even, so fft2 and ifft2 of it coincide up to the 1/(RC) factor
-    rc = fft2_general(b, R, 0.0, R, C, bs, workspace, fft_bytes, stream, /*real_input=*/true);
-    if (rc != SCINT_OK || !normalise) return rc;
-    const int blocks = max_blocks(R * C);
-    hipLaunchKernelGGL(max_partial_kernel, dim3(blocks), dim3(256), 0, stream, acf_out, R * C, partial);
-    hipLaunchKernelGGL(scale_by_max_kernel, dim3(blocks), dim3(256), 0, stream, acf_out, R * C, partial, blocks);
-    SCINT_LAUNCH_CHECK();
-    return SCINT_OK;
+    return acf_stack(dyn, 1, nf, nt, subtract_mean, normalise, acf_out, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
 // ------------------------------------------------------------------------------
 // scint_acf_batch: scint_acf of every problem of a stack [B][nf][nt] in launches that do not grow with B
 // ------------------------------------------------------------------------------
-// Per group of B problems: the means (2 launches, or a memset), the forward transform, the transform of the power, the maxima
-// and the division (2 launches) -- fft2_general's row and column passes with the problem as a range of slots / grid.z.
-// Moved per problem: 8 nf nt read; the complex intermediates (the row pass's result and the column working array of both
-// transforms, and the spectrum between them) written and read once each, 16 * 2nf * 2nt bytes apiece at power-of-two
-// lengths; 8 * 4 nf nt written, and read and written once more by the normalisation.
+// acf_stack above with the caller's B: the route scint_acf takes with B = 1.  The limits of the shape below are the stack's own
+// (grid.y and grid.z, the 32-bit row and tile-slot numbering of B problems); scint_acf has none of them.
 namespace scint {
 static bool acf_batch_shape_ok(int64_t B, int64_t nf, int64_t nt) {
     return B >= 1 && B <= 65535 && nf >= 1 && nt >= 1 && nf < (1 << 23) && nt < (1 << 23) && B * 2 * nf < (1 << 30) &&
@@ -1618,41 +1617,7 @@ extern "C" int32_t scint_acf_batch(const double* stack, int64_t B, int64_t nf, i
     size_t need = 0;
     scint_acf_batch_workspace_bytes(B, nf, nt, &need);
     if (workspace_bytes < need) { set_error("scint: acf_batch workspace too small"); return SCINT_E_WORKSPACE; }
-    hipStream_t stream = (hipStream_t)stream_;
-    const int64_t R = 2 * nf, C = 2 * nt;
-    const size_t fft_bytes = align_up(fft2_general_ws(R, C, R, B), 256);
-    Carver cv((char*)workspace + fft_bytes, workspace_bytes - fft_bytes);
-    cplx* spec = cv.take<cplx>((size_t)B * (size_t)R * (size_t)C);
-    double* partial = cv.take<double>((size_t)B * (size_t)max_blocks(R * C));      // (>= the mean's: R C = 4 nf nt)
-    double* scal = cv.take<double>((size_t)B);
-    if (subtract_mean) {
-        const int blocks = reduce_blocks(nf * nt);
-        hipLaunchKernelGGL(stack_sum_partial_kernel, dim3(blocks, (unsigned)B), dim3(256), 0, stream, stack, nf * nt, partial);
-        hipLaunchKernelGGL(stack_sum_final_kernel, dim3(1, (unsigned)B), dim3(256), 0, stream, (const double*)partial, blocks,
-                           1.0 / (double)(nf * nt), scal);
-        SCINT_LAUNCH_CHECK();
-    } else {
-        SCINT_HIP(hipMemsetAsync(scal, 0, sizeof(double) * (size_t)B, stream));
-    }
-    RowSource f{};
-    f.mode = SRC_ACF_IN; f.wv.dyn = stack; f.wv.nt = nt; f.wv.m1 = scal; f.prob_rows = (int)nf;
-    ColSink fs{};
-    fs.mode = SINK_ARRAY; fs.out_c = spec; fs.ld = C;
-    int32_t rc = fft2_general(f, nf, 0.0, R, C, fs, workspace, fft_bytes, stream, /*real_input=*/true, B, R * C);
-    if (rc != SCINT_OK) return rc;
-    RowSource b{};
-    b.mode = SRC_POWER; b.a = spec; b.ld = C;
-    ColSink bs{};
-    bs.mode = SINK_ACF; bs.out_d = acf_out; bs.scale = 1.0 / ((double)R * (double)C);
-    rc = fft2_general(b, R, 0.0, R, C, bs, workspace, fft_bytes, stream, /*real_input=*/true, B, R * C);
-    if (rc != SCINT_OK || !normalise) return rc;
-    const int blocks = max_blocks(R * C);
-    hipLaunchKernelGGL(stack_max_partial_kernel, dim3(blocks, (unsigned)B), dim3(256), 0, stream, (const double*)acf_out, R * C,
-                       partial);
-    hipLaunchKernelGGL(stack_scale_by_max_kernel, dim3(blocks, (unsigned)B), dim3(256), 0, stream, acf_out, R * C,
-                       (const double*)partial, blocks);
-    SCINT_LAUNCH_CHECK();
-    return SCINT_OK;
+    return acf_stack(stack, B, nf, nt, subtract_mean, normalise, acf_out, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
 // ------------------------------------------------------------------------------
@@ -1682,11 +1647,7 @@ extern "C" int32_t scint_acf_sspec(const double* sec_db, int64_t R, int64_t C, i
     fs.mode = SINK_ACF; fs.out_d = acf_out; fs.scale = 1.0;      // real(fftshift(fft2(.)))
     int32_t rc = fft2_general(f, R, 0.0, R, C, fs, workspace, fft_bytes, stream, /*real_input=*/true);
     if (rc != SCINT_OK || !normalise) return rc;
-    const int blocks = max_blocks(R * C);
-    hipLaunchKernelGGL(max_partial_kernel, dim3(blocks), dim3(256), 0, stream, acf_out, R * C, partial);
-    hipLaunchKernelGGL(scale_by_max_kernel, dim3(blocks), dim3(256), 0, stream, acf_out, R * C, partial, blocks);
-    SCINT_LAUNCH_CHECK();
-    return SCINT_OK;
+    return normalise_by_max(acf_out, 1, R * C, partial, stream);
 }
 
 // ------------------------------------------------------------------------------

@@ -4,7 +4,11 @@ fit_scint_params_2d_cut -- shared by the GPU tests (tests/test_gpu_acf_batch.py)
 
 The yardstick of the stack is the single call: problem k of the stack must hold the BITS of acf_device(stack[k]).  The single call's
 own yardstick is NumPy's statement of the reference, to the 1e-12 (of the ACF's maximum, 1 when normalised) that
-tests/test_gpu_scintpar.py allows it."""
+tests/test_gpu_scintpar.py allows it.
+
+The single calls are the B = 1 of the stacked routes (csrc/fft.hip: acf_stack, sspec_generic), which decode no problem there.  So
+the bit checks below no longer hold two implementations together: they guard the problem decode of the one route -- the row a
+problem's values and means are read from, the pairs of real rows formed inside a problem, its partials, its slice of the output."""
 import ctypes
 
 import numpy as np
@@ -40,7 +44,8 @@ def group_bytes(sp, name):
 
 
 def check_bits_of_the_single_call(sp, name):
-    """Problem k of the stack has the bits of acf_device(stack[k]) for every k and all four subtract_mean / normalise."""
+    """Problem k of the stack has the bits of acf_device(stack[k]) for every k and all four subtract_mean / normalise: the problem
+    decode of the one route (acf_device is its B = 1, which decodes nothing)."""
     x = to_dev(sp, cc.stack(name))
     gb = group_bytes(sp, name)
     if gb is not None:
@@ -151,7 +156,8 @@ SSPEC_FLAGS = [(False, True), (True, True), (False, False)]      # (prewhite, ha
 
 
 def check_sspec_bits_of_the_single_call(sp, name):
-    """Problem k of sspec_stack_device has the bits of sspec_device(stack[k]) for every k, prewhite and halve."""
+    """Problem k of sspec_stack_device has the bits of sspec_device(stack[k]) for every k, prewhite and halve: on the generic route
+    the problem decode of the one source (SRC_SSPEC; sspec_device is its B = 1), on `big` the persistent kernels run per problem."""
     from scintools_amd import dynspec
     x = to_dev(sp, cc.stack(name))
     B, nf, nt = cc.SHAPES[name]

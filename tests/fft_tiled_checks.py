@@ -231,7 +231,9 @@ def acf_ld(x):
 
 def check_acf_batch(sp, B, nf, nt):
     """scint_acf_batch: B problems in ONE tiled launch per pass.  Every problem has the bits of acf_device alone (the same build),
-    and the last one is the ACF to the single call's tolerance (tests/acf_batch_checks.py: 1e-12 of the maximum)."""
+    and the last one is the ACF to the single call's tolerance (tests/acf_batch_checks.py: 1e-12 of the maximum).  acf_device is
+    the B = 1 of the same route (csrc/fft.hip: acf_stack), which decodes no problem: the bit check guards the problem decode of
+    that one route -- the stacked rows, the tile slots' batch bits, the per-problem partials -- not two implementations."""
     import torch
     x = np.stack([tc.real_input(nf, nt, seed=20 + k) for k in range(B)])
     xt = sp.device.to_device(x, torch.float64)
